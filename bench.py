@@ -5,6 +5,7 @@ resident in HBM: OA-Mix (view 2 of every image) + Normalize/Pad on the device ->
 (both views) -> RPN/RoI losses incl. OA-Loss -> backward -> (DDP all-reduce) -> SGD step.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config r50_fpn|r101_dc5] [--workload train|oamix_stress]
+                  [--dump-outputs DIR]
 
 Default = BASELINE configs[1] (R50-FPN, bs 4, 1024x2048), the configuration the metric is quoted on.  ``--config r101_dc5``
 runs configs[3] (R101-DC5, bs 2, 736x1280) through the same machinery; ``--workload oamix_stress`` runs configs[4] (OA-Mix
@@ -114,6 +115,10 @@ def parse():
                     help='1: the data pipeline host code runs in a worker thread (DataLoader-worker analogue)')
     ap.add_argument('--conv', default='mfma', choices=['mfma', 'miopen'],
                     help='mfma: hand-written implicit-GEMM kernels where they apply; miopen: torch.conv2d only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed (loss, log variables, seeded samples of the '
+                         'updated parameters and their gradients; oamix_stress: loss, feature gradient, image samples) as '
+                         'DIR/<name>.npy (float32 / float64), at most 64 MB in all')
     a = ap.parse_args()
     wl = CONFIGS[a.config]
     for k in ('batch', 'height', 'width'):
@@ -451,7 +456,7 @@ def oamix_stress_run(a, rank, distributed, dev, affinity=None):
             es[2].record()
             ev['pass'].append((es[0], es[1]))
             ev['supcon'].append((es[1], es[2]))
-        return {'loss': loss, 'img2': data['img2']}
+        return {'loss': loss, 'img': data['img'], 'img2': data['img2']}
     np.random.seed(1000 + rank)
     for i in range(a.warmup):
         step(i)
@@ -460,6 +465,10 @@ def oamix_stress_run(a, rank, distributed, dev, affinity=None):
     clocks = ClockSampler(torch.cuda.current_device()).start() if rank == 0 else None
     dt, out = timed_region(step, a, distributed, dev, torch.cuda.synchronize)
     clock_summary = clocks.stop() if clocks is not None else None
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, {'loss': out['loss'], 'feats_grad': f.grad,
+                                      'img_sample': flat_sample([out['img']], seed=1),
+                                      'img2_sample': flat_sample([out['img2']], seed=2)})
     if rank != 0:
         return
     st = pipe.oamix.stats
@@ -563,6 +572,60 @@ def timed_region(step, a, distributed, dev, sync):
     return dt, out
 
 
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: all files together
+DUMP_SAMPLE = 1 << 22           # elements kept of one large output (a fixed, seeded sample)
+
+
+def sample_index(n, k=DUMP_SAMPLE, seed=0):
+    """the same sorted indices for the same n on every run and every build (own generator: the global streams the
+    workload draws from are not touched)"""
+    if n <= k:
+        return None
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+
+def flat_sample(tensors, seed=0):
+    """float32 vector of the elements of ``tensors`` (flattened and concatenated in order; a shape in place of a
+    tensor stands for that many zeros) at sample_index()"""
+    vecs = [t.detach().reshape(-1).float() if torch.is_tensor(t) else torch.zeros(int(np.prod(t)), dtype=torch.float32)
+            for t in tensors]
+    dev_ = next((v.device for v in vecs if v.is_cuda), torch.device('cpu'))
+    flat = torch.cat([v.to(dev_) for v in vecs])
+    idx = sample_index(flat.numel(), seed=seed)
+    if idx is not None:
+        flat = flat[torch.from_numpy(idx).to(dev_)]
+    return flat.cpu().numpy().astype(np.float32)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs DIR: one DIR/<name>.npy per output of the last timed step, float32 / float64"""
+    import re
+    os.makedirs(path, exist_ok=True)
+    out = {}
+    for name, v in arrays.items():
+        v = v.detach().float().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        out[re.sub(r'[^A-Za-z0-9_.-]', '_', name)] = v.astype(np.float64 if v.dtype == np.float64 else np.float32)
+    total = sum(v.nbytes for v in out.values())
+    assert total <= DUMP_LIMIT_BYTES, f'--dump-outputs: {total} bytes > {DUMP_LIMIT_BYTES}'
+    for name, v in out.items():
+        np.save(os.path.join(path, name + '.npy'), v)
+    print(f'dumped {len(out)} outputs ({total / 1e6:.1f} MB) to {path}', file=sys.stderr)
+
+
+def train_step_outputs(out, model=None):
+    """what a caller of the training step receives: the loss and log variables it returns, and the parameters it
+    updated (with the gradients the update used) - the last two as a seeded sample of the trainable parameters in
+    named order"""
+    arrays = {'loss': out['loss']}
+    arrays.update({f'log_vars.{k}': v for k, v in out['log_vars'].items() if torch.is_tensor(v) or isinstance(v, (int, float))})
+    if model is None:
+        return arrays
+    params = [p for _, p in model.named_parameters() if p.requires_grad]
+    arrays['params_sample'] = flat_sample(params)
+    arrays['grads_sample'] = flat_sample([p.grad if p.grad is not None else p.shape for p in params])
+    return arrays
+
+
 def plumbing_run(a, factory, rank, world, distributed, affinity=None):
     """see OADG_BENCH_STEP_FACTORY in main(): same control flow as the GPU run, CPU tensors, gloo"""
     import importlib
@@ -571,6 +634,8 @@ def plumbing_run(a, factory, rank, world, distributed, affinity=None):
     for i in range(a.warmup):
         wl['step'](i)
     dt, out = timed_region(wl['step'], a, distributed, torch.device('cpu'), lambda: None)
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, train_step_outputs(out))
     extras = wl['finish']() if 'finish' in wl else {}
     if rank != 0:
         return
@@ -708,6 +773,8 @@ def main():
     clocks = ClockSampler(torch.cuda.current_device()).start() if rank == 0 else None
     dt, out = timed_region(step, a, distributed, dev, torch.cuda.synchronize)
     clock_summary = clocks.stop() if clocks is not None else None
+    if rank == 0 and a.dump_outputs:             # before the per-family steps below move the parameters on
+        dump_outputs(a.dump_outputs, train_step_outputs(out, det))
     step = plain_step
     hip_conv.TIMERS = live
     conv_timers, hip_conv.TIMERS = hip_conv.TIMERS, None

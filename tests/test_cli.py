@@ -203,6 +203,7 @@ def test_bench_two_ranks_through_its_own_launch_path_on_gloo():
     env['PYTHONPATH'] = os.path.join(ROOT, 'tests') + os.pathsep + env.get('PYTHONPATH', '')
     env.pop('WORLD_SIZE', None)
     env['OMP_NUM_THREADS'] = '3'
+    env['OADG_AFFINITY_PROBE'] = '0'     # the first cores of each slice, not the quietest ones of the moment (host load)
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '0',
                         '--batch', '1', '--height', '128', '--width', '192', '--no-cpu-baseline'],
                        env=env, capture_output=True, text=True, timeout=850)
@@ -261,3 +262,61 @@ def test_bench_workloads_and_clock_sampler_without_a_gpu(monkeypatch):
     finally:
         os.sched_setaffinity(0, before)
         torch.set_num_threads(max(1, min(len(before), 16)))
+
+
+@pytest.mark.timeout(900)
+def test_bench_dump_outputs_are_the_last_timed_step_and_repeat(tmp_path):
+    """``bench.py --dump-outputs DIR`` (plumbing run on one CPU rank): DIR/<name>.npy in float32 / float64 holds what the last
+    of the --steps timed steps returned (its loss is the line's final_loss), and a second run with the same arguments
+    writes the same arrays"""
+    import json
+    import subprocess
+    env = dict(os.environ)
+    env['OADG_BENCH_STEP_FACTORY'] = 'ddp_bench_factory:make'
+    env['PYTHONPATH'] = os.path.join(ROOT, 'tests') + os.pathsep + env.get('PYTHONPATH', '')
+    env.pop('WORLD_SIZE', None)
+    env['OMP_NUM_THREADS'] = '3'
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f'run{run}'
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1',
+                            '--batch', '1', '--height', '128', '--width', '192', '--no-cpu-baseline', '--dump-outputs', str(d)],
+                           env=env, capture_output=True, text=True, timeout=850)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')][-1])
+        assert line['steps'] == 2 and line['ms_per_step'] > 0
+        arrays = {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+        assert {'loss', 'log_vars.loss_cls', 'log_vars.loss_cont'} <= set(arrays)
+        assert all(v.dtype in (np.float32, np.float64) for v in arrays.values())
+        assert round(float(arrays['loss']), 4) == line['config']['final_loss']
+        dumps.append(arrays)
+    assert set(dumps[0]) == set(dumps[1])
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
+
+
+def test_bench_dump_samples_are_fixed_and_bounded(tmp_path):
+    """the parameter / gradient samples of --dump-outputs: the same seeded indices for the same size on every call,
+    taken in named-parameter order (no gradient = zeros), and the 64 MB limit enforced"""
+    spec = importlib.util.spec_from_file_location('oadg_bench3', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n = bench.DUMP_SAMPLE + 12345
+    i0, i1 = bench.sample_index(n), bench.sample_index(n)
+    assert np.array_equal(i0, i1) and len(i0) == bench.DUMP_SAMPLE and (np.diff(i0) > 0).all() and i0[-1] < n
+    assert bench.sample_index(100) is None
+    torch.manual_seed(0)
+    m = torch.nn.ModuleList([torch.nn.Linear(2048, 2049), torch.nn.Linear(4, 4)])
+    m[0](torch.ones(2, 2048)).sum().backward()                   # the second layer receives no gradient
+    out = bench.train_step_outputs({'loss': torch.tensor(1.5), 'log_vars': {'acc': 50.0, 'note': 'x'}}, m)
+    assert set(out) == {'loss', 'log_vars.acc', 'params_sample', 'grads_sample'}
+    flat = torch.cat([p.detach().flatten() for p in m.parameters()]).numpy()
+    idx = bench.sample_index(flat.size)
+    assert np.array_equal(out['params_sample'], flat[idx])
+    n0 = sum(p.numel() for p in m[0].parameters())
+    assert (out['grads_sample'][idx >= n0] == 0).all() and np.count_nonzero(out['grads_sample'][idx < n0]) > 0
+    bench.dump_outputs(str(tmp_path / 'd'), out)
+    assert np.load(tmp_path / 'd' / 'log_vars.acc.npy').dtype == np.float64
+    assert np.load(tmp_path / 'd' / 'params_sample.npy').dtype == np.float32
+    with pytest.raises(AssertionError, match='--dump-outputs'):
+        bench.dump_outputs(str(tmp_path / 'big'), {'x': np.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1, np.float32)})
