@@ -543,35 +543,38 @@ class OAMix:
         """the work buffers of (image slot, lane): two ping-pong images, three region-op images with a scratch image each,
         histogram / LUT / grey-sum cells; the fp32 accumulator belongs to the slot (all lanes add into it).  Lane 0 is the
         only one outside the lockstep pass; inside it every mixture chain of a view records on a lane of its own, so that
-        ``execute`` may run the chains' per-box levels side by side."""
+        ``execute`` may run the chains' per-box levels side by side.
+
+        The cache holds one GROUP per (H, W, device, slot): the accumulator and the lane sets made so far, all of which
+        hold that very accumulator.  It is bounded by BYTES: a lane's set is 24 bytes per pixel (eight uint8
+        images = 50 MB at 1024 x 2048), the accumulator 12; per-sample multi-scale brings a new shape per image, so the
+        oldest groups go, WHOLE, once the cache holds more than OADG_OAMIX_CACHE_MB (default 2048: the lockstep pass of a
+        batch of eight with three lanes each plus headroom).  Every lane of a view and its final mix must use ONE
+        accumulator, so a group leaves only as a whole and the group being asked for never leaves: the cache may exceed
+        the bound by that one group, and then holds nothing else.  A set still referenced by recorded commands stays alive
+        through their closures."""
         lane = self._lane
-        key = (st.H, st.W, str(st.img.device), getattr(st, 'slot', 0), lane)
-        b = self._bufs.get(key)
+        key = (st.H, st.W, str(st.img.device), getattr(st, 'slot', 0))
+        g = self._bufs.get(key)
+        b = None if g is None else g['lanes'].get(lane)
         if b is None:
             dev, H, W = st.img.device, st.H, st.W
+            if g is None:
+                g = self._bufs[key] = dict(acc=torch.empty((H, W, 3), dtype=torch.float32, device=dev), lanes={},
+                                           bytes=12 * H * W)
             u8 = lambda: torch.empty((H, W, 3), dtype=torch.uint8, device=dev)  # noqa: E731
             sc = lambda: torch.empty((H * W * 3 + 4 * 8192 + 64,), dtype=torch.uint8, device=dev)  # noqa: E731
-            b = dict(ping=[u8(), u8()], tmp=[u8(), u8(), u8()], scratch=[sc(), sc(), sc()],
-                     hist=torch.empty((768,), dtype=torch.int32, device=dev),
-                     luts=torch.empty((2 * 768,), dtype=torch.uint8, device=dev),
-                     gray=torch.empty((1,), dtype=torch.int64, device=dev))
-            if lane == 0:
-                b['acc'] = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
-            else:
-                self._lane = 0
-                try:
-                    b['acc'] = self._buffers(st)['acc']
-                finally:
-                    self._lane = lane
-            # bounded by BYTES (ADVICE r4): a lane's set is 24 bytes per pixel (eight uint8 images = 50 MB at 1024 x 2048),
-            # the accumulator 12; per-sample multi-scale brings a new shape per image, so the oldest sets go once the cache
-            # holds more than OADG_OAMIX_CACHE_MB (default 2048: the lockstep pass of a batch of eight with three lanes
-            # each plus headroom).  A set still referenced by recorded commands stays alive through their closures.
-            b['bytes'] = (24 + (12 if lane == 0 else 0)) * H * W
+            b = g['lanes'][lane] = dict(ping=[u8(), u8()], tmp=[u8(), u8(), u8()], scratch=[sc(), sc(), sc()],
+                                        hist=torch.empty((768,), dtype=torch.int32, device=dev),
+                                        luts=torch.empty((2 * 768,), dtype=torch.uint8, device=dev),
+                                        gray=torch.empty((1,), dtype=torch.int64, device=dev), acc=g['acc'])
+            g['bytes'] += 24 * H * W
             limit = int(os.environ.get('OADG_OAMIX_CACHE_MB', 2048)) << 20
-            while self._bufs and sum(v['bytes'] for v in self._bufs.values()) + b['bytes'] > limit:
-                self._bufs.pop(next(iter(self._bufs)))
-            self._bufs[key] = b
+            total = sum(v['bytes'] for v in self._bufs.values())
+            for k in [k for k in self._bufs if k != key]:          # oldest first
+                if total <= limit:
+                    break
+                total -= self._bufs.pop(k)['bytes']
         return b
 
     # ------------------------------------------------------------------------------------------ regions

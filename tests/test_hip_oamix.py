@@ -427,3 +427,205 @@ def test_batched_image_states_equal_the_per_image_states(dev, monkeypatch):
     assert torch.equal(out[True]['img2'], out[False]['img2']) and torch.equal(out[True]['img'], out[False]['img'])
     for i in range(len(cases)):
         assert np.array_equal(out[True]['oamix_boxes'][i].numpy(), out[False]['oamix_boxes'][i].numpy())
+
+
+# ---------------------------------------------------------------------------------------------- mixed-shape batches
+MIXED_SEED = 1
+MIXED_PERM = (2, 0, 3, 1)           # the second batch: image k of it is image MIXED_PERM[k] of the first
+
+
+def _thin_boxes(rs, n, H, W):
+    """n boxes 3 px wide (or, every other one, 3 px high) starting at 4 k + 2.5: narrower than spatial_ratio, so their
+    saliency score is -1 and each is a mixing target, yet one cell wide at the masks' reduced resolution, so each has a
+    real (blurred) mask"""
+    out = np.zeros((n, 4), np.float32)
+    for i in range(n):
+        if i % 2 == 0:
+            x1, y1 = 4 * rs.randint(0, W // 4 - 2) + 2.5, rs.uniform(0, H - 31)
+            out[i] = (x1, y1, x1 + 3, y1 + rs.uniform(6, 30))
+        else:
+            x1, y1 = rs.uniform(0, W - 31), 4 * rs.randint(0, H // 4 - 2) + 2.5
+            out[i] = (x1, y1, x1 + rs.uniform(6, 30), y1 + 3)
+    return out
+
+
+def _mixed_shape_batch(seed):
+    """four uint8 images of different shapes (sides not multiples of 32, most not of 4): 7 boxes, none, 70 (64 of them
+    thin: more than MIX_TILES_MIN_TARGETS mixing targets, so the tile-binned final mix runs), 12"""
+    img0, g0 = _case(seed, 131, 253, 7)
+    img1, g1 = _case(seed + 1, 97, 130, 0)
+    rs = np.random.RandomState(seed + 2)
+    img2 = lowpass_image(rs, 256, 384, 4)
+    g2 = np.concatenate([synthetic_boxes(rs, 6, 256, 384, 6, 60), _thin_boxes(rs, 64, 256, 384)])
+    img3, g3 = _case(seed + 3, 200, 318, 12)
+    return [img0, img1, img2, img3], [g0, g1.reshape(0, 4), g2, g3]
+
+
+@pytest.fixture(scope='module')
+def mixed_shape_reference():
+    """the oracle on the images of two batches (the second one permuted), image after image from ONE seed - the order in
+    which the device pipeline consumes the stream; the stream's state after the first batch and its next double after the
+    second"""
+    imgs, gts = _mixed_shape_batch(MIXED_SEED)
+    np.random.seed(500 + MIXED_SEED)
+    batches, states = [], []
+    for order in (range(len(imgs)), MIXED_PERM):
+        refs = []
+        for i in order:
+            oracle = OO.OAMixOracle(version='augmix')
+            with np.errstate(all='ignore'):
+                r = oracle(dict(img=imgs[i].copy(), gt_bboxes=gts[i].copy()))
+            refs.append(dict(img2=r['img2'], multilevel_boxes=r['multilevel_boxes'], oamix_boxes=r['oamix_boxes'],
+                             fg_scores=[t[1] for t in oracle.trace if t[0] == 'fg_scores'][0],
+                             n_targets=sum(t[0] == 'm_oa' for t in oracle.trace)))
+        batches.append(refs)
+        states.append(np.random.get_state())
+    return imgs, gts, batches, states[0], np.random.random()
+
+
+def _norm_chw(u8):
+    """Normalize (mmcv.imnormalize with to_rgb) of a uint8 HWC BGR image in float32 numpy: CHW"""
+    mean = np.array([123.675, 116.28, 103.53], np.float32)
+    stdinv = (1.0 / np.array([58.395, 57.12, 57.375], np.float64)).astype(np.float32)
+    return np.ascontiguousarray(((u8[..., ::-1].astype(np.float32) - mean) * stdinv).transpose(2, 0, 1))
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int16 if t.dtype == torch.bfloat16 else torch.int32)
+
+
+def _assert_view(got, u8, h, w, what):
+    """got: [3, Hp, Wp] of a batch tensor.  Inside the image: Normalize of ``u8`` rounded to got's dtype (bf16: round to
+    nearest even of the float32 value), bit for bit; the padding: +0.0 exactly."""
+    want = torch.from_numpy(_norm_chw(u8)).to(got.dtype)
+    inner = _bits(got[:, :h, :w].cpu())
+    diff = inner != _bits(want)
+    assert not bool(diff.any()), f'{what}: {int(diff.sum())} of {diff.numel()} values differ'
+    assert not bool(_bits(got[:, h:, :].cpu()).any()) and not bool(_bits(got[:, :, w:].cpu()).any()), f'{what}: padding'
+
+
+def _mixed_pipeline(dtype, workers=None):
+    import os
+    from oadg_amd import Config
+    from oadg_amd.pipelines import DevicePipeline
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cfg = Config.fromfile(os.path.join(root, 'configs/oadg/faster_rcnn_r50_fpn_1x_cityscapes_oadg.py'))
+    assert not any(t['type'] in ('Resize', 'RandomFlip') for t in cfg.data.train.pipeline)
+    return DevicePipeline(cfg.data.train.pipeline, dtype=dtype, oamix_workers=workers)
+
+
+@pytest.mark.parametrize('cache_mb', [None, 1])
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16], ids=['f32', 'bf16'])
+def test_mixed_shape_batches_equal_the_oracle(dev, monkeypatch, mixed_shape_reference, dtype, cache_mb):
+    """A batch of differently shaped images (a list: the per-image path, as with per-sample multi-scale Resize) through
+    the lockstep pass, in float32 and in bf16 (the training dtype), with the default buffer cache and with one far too
+    small to hold a single buffer set (every miss evicts), then a second batch of the same images permuted through the
+    same pipeline (buffer sets of other shapes found in the slots, reused or evicted).  Per image: both views inside
+    img_shape equal Normalize of the oracle's bytes bit for bit, the padding is +0.0, the box lists equal the oracle's;
+    the numpy stream is consumed like the oracle's.  Both final-mix paths take part (tile-binned for the 70-box image)."""
+    from oadg_amd.pipelines import oa_mix
+    imgs, gts, ref, state_after_1, after_2 = mixed_shape_reference
+    for refs in ref:
+        fg = [s for r in refs for s in r['fg_scores'] if s >= 0]
+        assert not any(abs(s - 10) < 0.2 for s in fg), 'a saliency score sits on the decision threshold: pick other inputs'
+    assert [r['n_targets'] >= oa_mix.MIX_TILES_MIN_TARGETS for r in ref[0]] == [False, False, True, False]
+    if cache_mb is None:
+        monkeypatch.delenv('OADG_OAMIX_CACHE_MB', raising=False)
+    else:
+        monkeypatch.setenv('OADG_OAMIX_CACHE_MB', str(cache_mb))
+    L = oa_mix._lib.lib()
+    calls = []
+    for name in ('oadg_oamix_final', 'oadg_oamix_final_tiles'):
+        real = getattr(L, name)
+        monkeypatch.setattr(L, name, lambda *a, real=real, name=name: calls.append(name) or real(*a))
+    dimgs = [torch.from_numpy(im).to(dev) for im in imgs]
+    labels = [np.zeros(len(g), np.int64) for g in gts]
+    pipe = _mixed_pipeline(dtype)
+    np.random.seed(500 + MIXED_SEED)
+    for b, order in enumerate((range(len(imgs)), MIXED_PERM)):
+        calls.clear()
+        out = pipe([dimgs[i] for i in order], [gts[i] for i in order], [labels[i] for i in order])
+        torch.cuda.synchronize()
+        if b == 0:
+            st = np.random.get_state()
+            assert np.array_equal(st[1], state_after_1[1]) and st[2:] == state_after_1[2:], 'numpy stream after batch 1'
+        assert sorted(calls) == ['oadg_oamix_final'] * 3 + ['oadg_oamix_final_tiles']
+        assert out['img'].dtype == out['img2'].dtype == dtype
+        for k, i in enumerate(order):
+            h, w = imgs[i].shape[:2]
+            assert tuple(out['img_metas'][k]['img_shape'][:2]) == (h, w)
+            _assert_view(out['img'][k], imgs[i], h, w, f'batch {b} image {i} img')
+            _assert_view(out['img2'][k], ref[b][k]['img2'], h, w, f'batch {b} image {i} img2')
+            assert np.array_equal(out['oamix_boxes'][k].numpy(), ref[b][k]['oamix_boxes']), (b, i)
+            assert np.array_equal(out['multilevel_boxes'][k].numpy(), ref[b][k]['multilevel_boxes']), (b, i)
+    assert np.random.random() == after_2, 'the global numpy stream was consumed differently'
+
+
+def test_mixed_shape_helper_threads_do_not_depend_on_the_cache_limit(dev, monkeypatch, mixed_shape_reference):
+    """DevicePipeline(oamix_workers=2): each helper's OAMix clone has a buffer cache of its own.  From one seed, two
+    mixed-shape batches give the same bytes with the default cache and with one that evicts on every miss."""
+    imgs, gts = mixed_shape_reference[:2]
+    dimgs = [torch.from_numpy(im).to(dev) for im in imgs]
+    labels = [np.zeros(len(g), np.int64) for g in gts]
+    outs = {}
+    for cache_mb in (None, 1):
+        if cache_mb is None:
+            monkeypatch.delenv('OADG_OAMIX_CACHE_MB', raising=False)
+        else:
+            monkeypatch.setenv('OADG_OAMIX_CACHE_MB', str(cache_mb))
+        pipe = _mixed_pipeline(torch.bfloat16, workers=2)
+        np.random.seed(17)
+        outs[cache_mb] = [pipe([dimgs[i] for i in order], [gts[i] for i in order], [labels[i] for i in order])
+                          for order in (range(len(imgs)), MIXED_PERM)]
+        torch.cuda.synchronize()
+    for a, b in zip(outs[None], outs[1]):
+        assert torch.equal(_bits(a['img']), _bits(b['img']))
+        diff = _bits(a['img2']) != _bits(b['img2'])
+        assert not bool(diff.any()), int(diff.sum())
+        for k in range(len(imgs)):
+            assert np.array_equal(a['oamix_boxes'][k].numpy(), b['oamix_boxes'][k].numpy())
+            assert np.array_equal(a['multilevel_boxes'][k].numpy(), b['multilevel_boxes'][k].numpy())
+    assert not torch.equal(_bits(outs[None][0]['img2']), _bits(outs[None][0]['img']))
+
+
+def test_final_mix_tile_list_overflow_visits_every_target(dev, monkeypatch):
+    """mix_bins_kernel keeps at most 1024 targets per 32 x 32 tile; a tile reached by more falls back to visiting every
+    target.  1100 boxes of 3 x 3 px (score -1: every one is a target) clustered so that all their mask supports reach
+    tile (3, 3): the binned final mix must give the bytes of the unbinned one, and the tile counts it wrote show that the
+    fallback ran."""
+    from oadg_amd.pipelines import oa_mix
+    H, W, n = 256, 384, 1100
+    rs = np.random.RandomState(12)
+    img = lowpass_image(rs, H, W, 4)
+    x1 = 4 * rs.randint(24, 28, n) + 2.5
+    y1 = 4 * rs.randint(24, 28, n) + 2.5
+    gts = np.stack([x1, y1, x1 + 3, y1 + 3], 1).astype(np.float32)
+    L = oa_mix._lib.lib()
+    real = L.oadg_oamix_final_tiles
+    counts = []
+    tiles = ((W + 31) // 32) * ((H + 31) // 32)
+
+    def spy(*a):
+        rc = real(*a)
+        torch.cuda.synchronize()
+        ws = [s['mix_ws'] for g in pipe.oamix._bufs.values() for s in g['lanes'].values()
+              if 'mix_ws' in s and s['mix_ws'].data_ptr() == a[18].value]
+        assert len(ws) == 1, 'the workspace the call was given'
+        counts.append(ws[0][:4 * tiles].view(torch.int32).cpu().numpy())
+        return rc
+    monkeypatch.setattr(L, 'oadg_oamix_final_tiles', spy)
+    out, after = {}, {}
+    for binned in (True, False):
+        monkeypatch.setattr(oa_mix, 'MIX_TILES_MIN_TARGETS', 1 if binned else 1 << 30)
+        pipe = _mixed_pipeline(torch.float32)
+        np.random.seed(8)
+        seen = len(counts)
+        out[binned] = pipe(torch.from_numpy(img[None]).to(dev), [gts], [np.zeros(n, np.int64)])
+        torch.cuda.synchronize()
+        after[binned] = np.random.random()
+        assert len(counts) - seen == (1 if binned else 0)
+    c = counts[0].reshape((H + 31) // 32, (W + 31) // 32)
+    assert c[3, 3] >= n > 1024, c[3, 3]
+    assert after[True] == after[False]
+    assert torch.equal(out[True]['img2'], out[False]['img2'])
+    assert not torch.equal(out[True]['img2'], out[True]['img'])
