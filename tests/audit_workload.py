@@ -1,0 +1,66 @@
+"""The audited training steps shared by tests/test_conv_audit.py and tests/test_head_audit.py: the detector, optimizer and
+device pipeline built as bench.py main() builds them, one unaudited step (its optimizer step refreshes the prepared-weight
+bank), then a second step run under an auditor."""
+import os
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+R50_CFG = os.path.join(ROOT, 'configs', 'oadg', 'faster_rcnn_r50_fpn_1x_cityscapes_oadg.py')
+DC5_CFG = os.path.join(ROOT, 'configs', 'oadg', 'faster_rcnn_r101_dc5_1x_dwd_oadg.py')
+
+
+def audited_step(dev, monkeypatch, cfg_path, batch, H, W, boxes, classes, box_size, install, on_begin=None,
+                 on_end_backward=None, before_step1=None):
+    """(out of the audited step, det, wall seconds).  ``install(monkeypatch, det)`` wraps the entry points after step 1;
+    ``on_begin()`` / ``on_end_backward(det)`` run inside hip_conv.begin_step / end_backward of the audited step;
+    ``before_step1(monkeypatch, det)`` may wrap something for step 1 as well (it stays installed for step 2)."""
+    from oadg_amd import Config, build_detector, hip_conv
+    from oadg_amd.apis import TrainEngine, build_optimizer, set_random_seed
+    from oadg_amd.pipelines import DevicePipeline, SyntheticCityscapes
+    cfg = Config.fromfile(cfg_path)
+    hip_conv.enable()
+    try:
+        set_random_seed(0)                       # bench.py main(): the same construction
+        det = build_detector(cfg.model)
+        det.init_weights(allow_missing_pretrained=True)
+        det = det.to(dev).to(memory_format=torch.channels_last).train()
+        det.log_vars_on_host = False
+        engine = TrainEngine(det, build_optimizer(det, cfg.optimizer), amp_dtype=torch.bfloat16)
+        set_random_seed(1)
+        ds = SyntheticCityscapes(img_shape=(H, W), num_boxes=boxes, num_classes=classes, box_size=box_size, seed=0,
+                                 device=dev)
+        pipe = DevicePipeline(cfg.data.train.pipeline, dtype=torch.bfloat16)
+        if before_step1 is not None:
+            before_step1(monkeypatch, det)
+        engine.step(pipe(*ds.batch(range(batch))))          # step 1: its optimizer step refreshes the prepared-weight bank
+        data = pipe(*ds.batch(range(batch, 2 * batch)))
+        torch.cuda.synchronize()
+
+        install(monkeypatch, det)
+        begin, end = hip_conv.begin_step, hip_conv.end_backward
+
+        def begin_step(defer):
+            assert defer, 'the audited step must take the deferred path of TrainEngine._step'
+            if on_begin is not None:
+                on_begin()
+            return begin(defer)
+
+        def end_backward():
+            n = end()
+            torch.cuda.synchronize()
+            if on_end_backward is not None:
+                on_end_backward(det)
+            return n
+        monkeypatch.setattr(hip_conv, 'begin_step', begin_step)
+        monkeypatch.setattr(hip_conv, 'end_backward', end_backward)
+        t0 = time.perf_counter()
+        out = engine.step(data)                             # step 2: audited
+        torch.cuda.synchronize()
+        wall = time.perf_counter() - t0
+        monkeypatch.undo()
+        assert torch.isfinite(out['loss']).all()
+        return out, det, wall
+    finally:
+        hip_conv.enable(False)

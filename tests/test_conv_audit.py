@@ -5,17 +5,11 @@ GPU tests (``-m gpu``): three workloads on the deferred path TrainEngine._step t
 exceeds its bound, that every wrapper expected for the network saw a call, and that the set of audited kernel
 instantiations equals the list written here (a launch routed around the auditor, or a new instantiation, fails the test).
 """
-import os
-import time
-
 import pytest
 import torch
 
 import conv_audit as CA
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-R50_CFG = os.path.join(ROOT, 'configs', 'oadg', 'faster_rcnn_r50_fpn_1x_cityscapes_oadg.py')
-DC5_CFG = os.path.join(ROOT, 'configs', 'oadg', 'faster_rcnn_r101_dc5_1x_dwd_oadg.py')
+from audit_workload import DC5_CFG, R50_CFG, audited_step
 
 
 # ------------------------------------------------------------------------------------------- CPU self-tests of the checker
@@ -359,56 +353,23 @@ WRAPPERS['r101_dc5'] = WRAPPERS['r50_fpn'] - {'_NarrowHead.forward', '_NarrowHea
 
 
 def _audited_step(dev, monkeypatch, cfg_path, batch, H, W, boxes, classes, box_size, key):
-    from oadg_amd import Config, build_detector, hip_conv
-    from oadg_amd.apis import TrainEngine, build_optimizer, set_random_seed
-    from oadg_amd.pipelines import DevicePipeline, SyntheticCityscapes
-    cfg = Config.fromfile(cfg_path)
-    hip_conv.enable()
-    try:
-        set_random_seed(0)                       # bench.py main(): the same construction
-        det = build_detector(cfg.model)
-        det.init_weights(allow_missing_pretrained=True)
-        det = det.to(dev).to(memory_format=torch.channels_last).train()
-        det.log_vars_on_host = False
-        engine = TrainEngine(det, build_optimizer(det, cfg.optimizer), amp_dtype=torch.bfloat16)
-        set_random_seed(1)
-        ds = SyntheticCityscapes(img_shape=(H, W), num_boxes=boxes, num_classes=classes, box_size=box_size, seed=0,
-                                 device=dev)
-        pipe = DevicePipeline(cfg.data.train.pipeline, dtype=torch.bfloat16)
-        engine.step(pipe(*ds.batch(range(batch))))          # step 1: its optimizer step refreshes the prepared-weight bank
-        data = pipe(*ds.batch(range(batch, 2 * batch)))
-        torch.cuda.synchronize()
+    A = CA.Auditor()
+    checked = []
 
-        A = CA.Auditor().install(monkeypatch)
-        checked = []
-        begin, end = hip_conv.begin_step, hip_conv.end_backward
+    def on_begin():
+        A.params.clear()
+        A.bf16_handover.clear()
+        A.narrow = None
 
-        def begin_step(defer):
-            assert defer, 'the audited step must take the deferred path of TrainEngine._step'
-            A.params.clear()
-            A.bf16_handover.clear()
-            A.narrow = None
-            return begin(defer)
+    def on_end_backward(det):
+        head = det.rpn_head
+        checked.append(A.check_params(list(det.named_parameters()), [head.rpn_cls, head.rpn_reg]))
 
-        def end_backward():
-            n = end()
-            torch.cuda.synchronize()
-            head = det.rpn_head
-            checked.append(A.check_params(list(det.named_parameters()), [head.rpn_cls, head.rpn_reg]))
-            return n
-        monkeypatch.setattr(hip_conv, 'begin_step', begin_step)
-        monkeypatch.setattr(hip_conv, 'end_backward', end_backward)
-        t0 = time.perf_counter()
-        out = engine.step(data)                             # step 2: audited
-        torch.cuda.synchronize()
-        wall = time.perf_counter() - t0
-        monkeypatch.undo()
-        A.print_table('%s (audited step %.1f s)' % (key, wall))
-        print('worst err / bound: %.4f' % A.worst())
-        assert torch.isfinite(out['loss']).all()
-        return A, det, checked[-1], wall
-    finally:
-        hip_conv.enable(False)
+    out, det, wall = audited_step(dev, monkeypatch, cfg_path, batch, H, W, boxes, classes, box_size,
+                                  lambda mp, det: A.install(mp), on_begin, on_end_backward)
+    A.print_table('%s (audited step %.1f s)' % (key, wall))
+    print('worst err / bound: %.4f' % A.worst())
+    return A, det, checked[-1], wall
 
 
 def _assert_audit(A, det, checked, key, expected_params):
