@@ -5,7 +5,7 @@ resident in HBM: OA-Mix (view 2 of every image) + Normalize/Pad on the device ->
 (both views) -> RPN/RoI losses incl. OA-Loss -> backward -> (DDP all-reduce) -> SGD step.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config r50_fpn|r101_dc5] [--workload train|oamix_stress]
-                  [--dump-outputs DIR]
+                  [--dump-outputs DIR] [--full]
 
 Default = BASELINE configs[1] (R50-FPN, bs 4, 1024x2048), the configuration the metric is quoted on.  ``--config r101_dc5``
 runs configs[3] (R101-DC5, bs 2, 736x1280) through the same machinery; ``--workload oamix_stress`` runs configs[4] (OA-Mix
@@ -20,7 +20,12 @@ run directly (no WORLD_SIZE in the environment), re-launched under torch.distrib
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
   "roofline"     - the dominant hand-written kernel of the step, timed live with HIP events on its stream
-  "cpu_baseline" - the CPU oracle (kind "port") timed on this box's host cores on a bounded sample (rank 0, N=1)
+  "cpu_baseline" - the CPU oracle (kind "port") timed on this box's host cores on a bounded sample (--full, rank 0, N=1)
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, dump (--dump-outputs) and print.
+``--full`` adds what takes runs of its own after the timed region: the per-family table (``roofline.families`` /
+``top_shapes``: 3 more steps with event pairs around every launch; skip with --no-families) and the CPU baseline (about
+30 s of host time; skip with --no-cpu-baseline).  The timed steps and the headline figures are the same either way.
 """
 import argparse
 import json
@@ -109,8 +114,11 @@ def parse():
     ap.add_argument('--height', type=int, default=None)
     ap.add_argument('--width', type=int, default=None)
     ap.add_argument('--dtype', default='bf16', choices=['bf16', 'fp32'])
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-families', action='store_true', help='skip the per-family table (3 extra steps after the timed region)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what runs after the timed region: the per-family table and the CPU baseline')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
+    ap.add_argument('--no-families', action='store_true',
+                    help='--full without the per-family table (3 extra steps after the timed region)')
     ap.add_argument('--pipeline-thread', type=int, default=1,
                     help='1: the data pipeline host code runs in a worker thread (DataLoader-worker analogue)')
     ap.add_argument('--conv', default='mfma', choices=['mfma', 'miopen'],
@@ -126,6 +134,13 @@ def parse():
             setattr(a, k, 8 if (a.workload == 'oamix_stress' and k == 'batch') else
                     (CONFIGS['r50_fpn'][k] if a.workload == 'oamix_stress' else wl[k]))
     return a
+
+
+def full_extras(a):
+    """(per-family table, CPU baseline): what this run measures after its timed region - only with --full, and only on a
+    single GPU (rank 0 is then alone: nobody else is measuring)"""
+    one = a.full and a.gpus == 1
+    return one and not a.no_families, one and not a.no_cpu_baseline
 
 
 class ClockSampler:
@@ -505,7 +520,7 @@ def oamix_stress_run(a, rank, distributed, dev, affinity=None):
                                   f'+ Normalize/Pad; OA-Loss at B = {B} rows', 'global_batch': a.gpus * a.batch,
                       'parallelism': f'dp{a.gpus}', 'final_loss': round(float(out['loss'].detach()), 5), 'cpu_affinity': affinity},
            'clocks': clock_summary, 'roofline': roof,
-           'cpu_baseline': None if (a.no_cpu_baseline or a.gpus != 1) else stress_cpu_baseline(H, W)}
+           'cpu_baseline': stress_cpu_baseline(H, W) if full_extras(a)[1] else None}
     print(json.dumps(res))
 
 
@@ -753,7 +768,7 @@ def main():
     # the largest single kernel of the step - the 256-tile forward / data-gradient kernel and the 256-tile weight-gradient
     # kernels (~90 pairs, ~0.4 ms on such a step, ~0.1 ms per step on average) - and the kernel with the largest total
     # over those steps is reported (round 3 chose the family from a 2-step warm-up probe: two kernels within 5 % of each
-    # other swapped places from run to run).  The other families are measured on extra steps AFTER the timed region.
+    # other swapped places from run to run).  The other families are measured on extra steps AFTER the timed region (--full).
     sample_every = int(os.environ.get('OADG_BENCH_SAMPLE_EVERY', 4))
     sampled_steps = [0]
     live = [] if mfma else None
@@ -783,7 +798,7 @@ def main():
     # ---- per-family table: DIAG_STEPS more steps with event pairs around every convolution / weight-gradient launch,
     #      RoIAlign forward / backward, the OA-Loss kernels and the OA-Mix per-box chains (worker thread, side stream)
     diag_conv, diag_ops, diag_steps = [], {}, 0
-    if rank == 0 and a.gpus == 1 and not a.no_families:
+    if rank == 0 and full_extras(a)[0]:
         diag_steps = 3
         hip_ops.TIMERS = {k: [] for k in ('roi_align_fwd', 'roi_align_bwd', 'supcon_fwd', 'supcon_bwd', 'oamix_bbox_chain')}
         if mfma:
@@ -893,7 +908,7 @@ def main():
         n_ = max(engine.reducer.steps, 1)
         res['config']['grad_mb_in_place_per_step'] = round(engine.reducer.in_place_bytes / n_ / 1e6, 1)
         res['config']['grad_mb_packed_per_step'] = round(engine.reducer.packed_bytes / n_ / 1e6, 1)
-    if a.gpus == 1 and not a.no_cpu_baseline:
+    if full_extras(a)[1]:
         res['cpu_baseline'] = cpu_baseline(cfg, dict(wl, batch=a.batch, height=a.height, width=a.width))
     else:
         res['cpu_baseline'] = None

@@ -243,6 +243,13 @@ def test_bench_workloads_and_clock_sampler_without_a_gpu(monkeypatch):
     monkeypatch.setattr(sys, 'argv', ['bench.py', '--config', 'r101_dc5'])
     a = bench.parse()
     assert (a.batch, a.height, a.width, a.workload) == (2, 736, 1280, 'train')
+    # (per-family table, CPU baseline): only with --full, only on one GPU, and --no-families / --no-cpu-baseline drop either
+    for argv, want in (([], (False, False)), (['--no-cpu-baseline'], (False, False)), (['--full'], (True, True)),
+                       (['--full', '--no-cpu-baseline'], (True, False)), (['--full', '--no-families'], (False, True)),
+                       (['--full', '--workload', 'oamix_stress'], (True, True)), (['--full', '--gpus', '2'], (False, False))):
+        monkeypatch.setattr(sys, 'argv', ['bench.py', '--steps', '20', '--warmup', '5'] + argv)
+        a = bench.parse()
+        assert a.full == ('--full' in argv) and bench.full_extras(a) == want, argv
     s = bench.ClockSampler(0).start().stop()
     assert s['available'] in (True, False) and ('sclk_mhz' in s or 'note' in s)
     # a single rank is pinned too (a compact set of physical cores: the run-to-run spread of the host time), the CPU-baseline

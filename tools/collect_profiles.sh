@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 # CONFIG=r101_dc5 PREFIX=dc5_ collects the same summaries for the other bench configuration (files <PREFIX>kernel_stats.csv ...)
 CONFIG=${CONFIG:-r50_fpn}
 PREFIX=${PREFIX:-}
-CMD="python bench.py --config $CONFIG --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline"
+CMD="python bench.py --full --config $CONFIG --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline"
 if [ "${SKIP_STATS:-0}" != "1" ]; then
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_${PREFIX}stats -o b -- $CMD > $OUT/${PREFIX}bench_under_rocprof.log 2>&1
 cp $(find /tmp/p_${PREFIX}stats -name "*kernel_stats.csv" | head -1) $OUT/${PREFIX}kernel_stats.csv
