@@ -10,8 +10,8 @@
  *   - every pointer is a DEVICE pointer unless its name ends in `_host`; the caller owns all memory
  *   - `stream` is a hipStream_t passed as void*; calls only enqueue work: no allocation, no
  *     synchronisation, no global mutable state (re-entrant across streams with distinct workspaces)
- *   - return value: 0 = ok, < 0 = argument error (OADG_EARG -1, OADG_ESIZE -2; the host-side file decoder also
- *     OADG_EIO -3, OADG_EUNSUPPORTED -4), > 0 = hipError_t
+ *   - return value: 0 = ok, < 0 = argument error (OADG_EARG -1, OADG_ESIZE -2; the host-side file decoders also
+ *     OADG_EIO -3, OADG_EUNSUPPORTED -4, OADG_EFORMAT -5), > 0 = hipError_t
  *   - tensors are dense row-major in the stated shape; images/feature maps are NHWC
  */
 #ifndef OADG_HIP_H
@@ -319,6 +319,52 @@ int oadg_oamix_normalize(const uint8_t* img, int H, int W, const float* mean_hos
  * file's extent is not H x W, OADG_EIO when it cannot be read.  oadg_png_size: the extent from the header. */
 int oadg_png_size(const char* path, int* height, int* width);
 int oadg_png_decode_bgr(const char* path, uint8_t* out, int H, int W);
+
+/* ------------------------------------------------------------------------------------------------
+ * JPEG input files (csrc/jpeg_decode.hip): entropy stage on the HOST, pixel stage on the DEVICE
+ *   every entry below: LoadImageFromFile  mmdet/datasets/pipelines/loading.py:18-98 (mmcv.imfrombytes -> cv2.imdecode: colour,
+ *             BGR byte order; libjpeg-turbo's defaults: islow IDCT, fancy upsampling)
+ * Byte-equal to PIL / OpenCV.  Covers SOF0 / SOF1, 8-bit, Huffman, one scan holding every component, 8- or 16-bit DQT,
+ * restart intervals; grey, or YCbCr with luma sampling 1x1 / 2x1 / 2x2 and chroma 1x1.  Any other variant (progressive,
+ * arithmetic, lossless, 12-bit, multi-scan, CMYK, RGB-coded, other sampling, DNL) returns OADG_EUNSUPPORTED and a truncated
+ * or corrupt stream OADG_EFORMAT: the caller decodes that file with PIL.  OADG_ESIZE when the file's extent is not H x W,
+ * OADG_EIO when it cannot be read.
+ *
+ * oadg_jpeg_desc: what the pixel stage needs of one image.  Each component's coefficients cover its MCU-padded block grid
+ * (bw x bh blocks, row-major), starting `off` int16 elements into the image's slot; each block holds its 64 QUANTIZED
+ * coefficients column-major (element u * 8 + v = horizontal frequency u, vertical frequency v), and `qt` the component's
+ * quantization table in the same order.  The pixel stage dequantizes in int32. */
+typedef struct oadg_jpeg_desc {
+    int32_t height, width;  /* image extent */
+    int32_t ncomp;          /* 1 (grey) or 3 (YCbCr); 0 = not decoded natively: the pixel stage leaves that image alone */
+    int32_t hmax, vmax;     /* luma sampling factors (1 for grey) */
+    int32_t mcux, mcuy;     /* MCUs per row, MCU rows */
+    int32_t reserved;
+    int32_t h[4], v[4];     /* sampling factors of each component */
+    int32_t bw[4], bh[4];   /* block grid of each component: mcux * h blocks per row, mcuy * v block rows */
+    int32_t cw[4], ch[4];   /* true extent of each component in samples: ceil(W h / hmax) x ceil(H v / vmax) */
+    int64_t off[4];         /* first coefficient of each component, in int16 elements from the image's slot */
+    uint16_t qt[4][64];     /* quantization table of each component, column-major */
+} oadg_jpeg_desc;           /* 672 bytes */
+
+/* oadg_jpeg_size: the extent from the frame header (of any JPEG frame type).  oadg_jpeg_coef_capacity: int16 elements
+ * of coefficients an H x W image can need (3 per pixel of the extent rounded up to 16 on each side: 6 bytes) - the
+ * slot size of the batch buffers below. */
+int oadg_jpeg_size(const char* path, int* height, int* width);
+size_t oadg_jpeg_coef_capacity(int H, int W);
+/* HOST: markers, Huffman decoding (DC prediction, restart resets) -> the quantized coefficients at coef_host (capacity
+ * int16 elements; OADG_ESIZE when short) and the descriptor at desc_host (ncomp = 0 on any failure).  One call per image,
+ * re-entrant; the data set runs it on its decode threads without the interpreter lock, into a pinned buffer. */
+int oadg_jpeg_entropy_decode(const char* path, int H, int W, int16_t* coef_host, size_t capacity,
+                             oadg_jpeg_desc* desc_host);
+/* DEVICE: n images of one extent H x W -> out uint8 [n][H][W][3] (B, G, R).  coef: image i's slot at i * slot int16
+ * elements (slot >= oadg_jpeg_coef_capacity(H, W), a multiple of 64); desc: n descriptors (16-byte aligned); planes:
+ * n * slot bytes of workspace (the component planes).  Two launches: IDCT into the planes, then upsampling + colour
+ * conversion into out.  Images whose descriptor has ncomp 0 or another extent are not written. */
+int oadg_jpeg_pixels_bgr(const int16_t* coef, const oadg_jpeg_desc* desc, int n, long long slot, uint8_t* planes,
+                         uint8_t* out, int H, int W, void* stream);
+/* HOST twin of the two stages (the same IDCT, upsampling and colour code): JPEG file -> uint8 [H][W][3] BGR at out. */
+int oadg_jpeg_decode_bgr(const char* path, uint8_t* out, int H, int W);
 
 /* ------------------------------------------------------------------------------------------------
  * Robustness-benchmark corruptions (HOST functions, no device work; csrc/corrupt_host.hip) - the two sequential

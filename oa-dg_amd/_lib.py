@@ -166,6 +166,11 @@ SIGNATURES = {
     'oadg_oamix_bbox_chain_multi': (ci, [vp, ci, vp]),
     'oadg_png_size': (ci, [c_char_p, POINTER(ci), POINTER(ci)]),
     'oadg_png_decode_bgr': (ci, [c_char_p, vp, ci, ci]),
+    'oadg_jpeg_size': (ci, [c_char_p, POINTER(ci), POINTER(ci)]),
+    'oadg_jpeg_coef_capacity': (cs, [ci, ci]),
+    'oadg_jpeg_entropy_decode': (ci, [c_char_p, ci, ci, vp, cs, vp]),
+    'oadg_jpeg_pixels_bgr': (ci, [vp, vp, ci, ctypes.c_longlong, vp, vp, ci, ci, vp]),
+    'oadg_jpeg_decode_bgr': (ci, [c_char_p, vp, ci, ci]),
     'oadg_glass_shuffle_u8': (ci, [vp, ci, ci, ci, ci, ci, vp]),
     'oadg_chamfer_l2_5x5': (ci, [vp, ci, ci, vp]),
     'oadg_oamix_compose': (ci, [vp, vp, ci, ci, POINTER(RegionOp), POINTER(ci), ci, vp, vp, vp, vp, cf, ci, vp]),

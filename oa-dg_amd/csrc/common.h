@@ -9,6 +9,7 @@
 #define OADG_ESIZE (-2)    // workspace too small
 #define OADG_EIO (-3)      // host file could not be read (png_decode.hip)
 #define OADG_EUNSUPPORTED (-4)   // a file format variant the native decoder does not cover (the caller falls back)
+#define OADG_EFORMAT (-5)   // a truncated or corrupt file (jpeg_decode.hip; the caller hands it to PIL)
 
 #define OADG_WAVE 64
 

@@ -6,10 +6,16 @@ needs (``load_annotations``, ``_filter_imgs``, ``_parse_ann_info``, ``get_ann_in
 functions use (pycocotools is not installed).  Images are decoded on the host (PIL; PNG is lossless, so the bytes equal
 ``mmcv.imfrombytes(..., flag='color')`` = BGR order) by a small thread pool and uploaded through pinned memory; from
 there on everything is the device pipeline.  ``batch(indices)`` has ``SyntheticCityscapes``' signature.
+
+JPEG files of a dataset on the GPU take the native path (csrc/jpeg_decode.hip): the decode threads run the entropy stage
+into one pinned coefficient buffer, one upload carries it to the device and the pixel stage writes the batch there,
+byte-equal to PIL.  ``XMLDataset`` / ``SdgodDataset`` (mmdet/datasets/{xml_style,sdgod}.py: VOC-style id lists, XML
+annotations, JPEG frames - the Diverse-Weather benchmark) reuse all of it.
 """
 import json
 import os
 import threading
+import xml.etree.ElementTree as ET
 from collections import defaultdict
 from concurrent.futures import ThreadPoolExecutor
 
@@ -20,6 +26,8 @@ from .registry import DATASETS, build_from_cfg
 
 
 NATIVE_PNG = os.environ.get('OADG_NATIVE_PNG', '1') == '1'     # PNG files through csrc/png_decode.hip (else PIL)
+NATIVE_JPEG = os.environ.get('OADG_NATIVE_JPEG', '1') == '1'   # JPEG files of a GPU dataset through csrc/jpeg_decode.hip
+_JPEG_EXT = ('.jpg', '.jpeg')
 
 
 class _CocoIndex:
@@ -86,6 +94,9 @@ class CocoDataset:
         self.decode_workers = want
         self.ring_slots = 6            # pinned batch buffers per (batch, shape): more than tools/train.py keeps in flight
         self._rings, self._ring_lock = {}, threading.Lock()
+        self._coef_rings = {}          # pinned JPEG coefficient buffers, keyed by capacity (a power of two)
+        self.jpeg_decodes = dict(native=0, pil=0)       # JPEG files decoded by csrc/jpeg_decode.hip / by PIL
+        self._count_lock = threading.Lock()
         self._pool = ThreadPoolExecutor(want, thread_name_prefix='oadg-decode', initializer=self._place_worker)
         # custom.py:209-221 _set_group_flag: images with aspect ratio > 1 form group 1 (the samplers group by it)
         self.flag = np.array([1 if i['width'] / i['height'] > 1 else 0 for i in self.data_infos], dtype=np.uint8)
@@ -186,6 +197,8 @@ class CocoDataset:
         decoder (csrc/png_decode.hip: one call without the interpreter lock, pixels written at their final place); any other
         format, or a PNG variant it does not cover, through PIL."""
         path = self._path(idx)
+        if path.lower().endswith(_JPEG_EXT):
+            self._count('pil')
         if NATIVE_PNG and path.lower().endswith('.png'):
             from . import _lib
             rc = _lib.lib().oadg_png_decode_bgr(path.encode(), dst.ctypes.data, dst.shape[0], dst.shape[1])
@@ -199,14 +212,26 @@ class CocoDataset:
         info = self.data_infos[idx]
         return int(info['height']), int(info['width'])
 
+    def _count(self, path, k=1):
+        with self._count_lock:
+            self.jpeg_decodes[path] += k
+
     def _slot(self, n, H, W):
         """a pinned [n,H,W,3] batch buffer from a small ring (allocated once per shape: pinning 25 MB per batch costs more
         than decoding it); a slot is reused only after the upload that read it has finished"""
-        key = (n, H, W)
+        return self._ring_slot(self._rings, (n, H, W), lambda: torch.empty((n, H, W, 3), dtype=torch.uint8))
+
+    def _coef_slot(self, nbytes):
+        """a pinned uint8 buffer of at least ``nbytes`` for the JPEG coefficients + descriptors of a batch, from a ring
+        keyed by capacity (the next power of two, at least 1 MiB): a handful of rings whatever the image shapes"""
+        cap = 1 << max(20, (int(nbytes) - 1).bit_length())
+        return self._ring_slot(self._coef_rings, cap, lambda: torch.empty(cap, dtype=torch.uint8))
+
+    def _ring_slot(self, rings, key, alloc):
         with self._ring_lock:
-            ring = self._rings.setdefault(key, dict(bufs=[], events=[], next=0))
+            ring = rings.setdefault(key, dict(bufs=[], events=[], next=0))
             if len(ring['bufs']) < self.ring_slots:
-                buf = torch.empty((n, H, W, 3), dtype=torch.uint8)
+                buf = alloc()
                 if torch.device(self.device).type == 'cuda':
                     buf = buf.pin_memory()
                 ring['bufs'].append(buf)
@@ -226,6 +251,11 @@ class CocoDataset:
         shapes = {self._shape(i) for i in indices}
         assert len(shapes) == 1, 'one image shape per batch (Cityscapes: 1024x2048)'
         H, W = shapes.pop()
+        if torch.device(self.device).type == 'cuda' and NATIVE_JPEG and \
+                any(self._path(i).lower().endswith(_JPEG_EXT) for i in indices):
+            dev = self._batch_jpeg(indices, H, W)
+            anns = [self.get_ann_info(i) for i in indices]
+            return dev, [a['bboxes'] for a in anns], [a['labels'] for a in anns]
         ring, k = self._slot(len(indices), H, W)
         host = ring['bufs'][k]
         views = host.numpy()
@@ -240,6 +270,48 @@ class CocoDataset:
         anns = [self.get_ann_info(i) for i in indices]
         return dev, [a['bboxes'] for a in anns], [a['labels'] for a in anns]
 
+    def _batch_jpeg(self, indices, H, W):
+        """uint8 [N,H,W,3] on the device for a batch holding JPEG files: the decode threads run the entropy stage of each
+        JPEG into its slot of one pinned buffer (descriptors first, then one coefficient slot per image), one upload, the
+        pixel stage on the current stream.  A file the native path declines or fails on (and any other file) is decoded
+        as ``decode_into`` does it and copied into its place, so its bytes - or its error - are the PIL path's."""
+        from . import _lib, hip_ops
+        L = _lib.lib()
+        n, D = len(indices), hip_ops.JPEG_DESC_BYTES
+        slot = int(L.oadg_jpeg_coef_capacity(H, W))
+        dbytes = n * D                                   # (a multiple of 16: the coefficients stay 16-byte aligned)
+        need = dbytes + 2 * n * slot
+        ring, k = self._coef_slot(need)
+        host = ring['bufs'][k]
+        arr = host.numpy()
+        base = arr.ctypes.data
+
+        def work(a):
+            i, idx = a
+            path = self._path(idx)
+            arr[i * D:(i + 1) * D] = 0                   # ncomp 0: the pixel stage leaves this image alone
+            if path.lower().endswith(_JPEG_EXT):
+                rc = L.oadg_jpeg_entropy_decode(path.encode(), H, W, base + dbytes + 2 * i * slot, slot, base + i * D)
+                if rc == 0:
+                    return None
+            img = np.empty((H, W, 3), dtype=np.uint8)
+            self.decode_into(idx, img)
+            return img
+        host_imgs = list(self._pool.map(work, enumerate(indices)))
+        native = sum(a is None for a in host_imgs)
+        self._count('native', native)
+        out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=self.device)
+        if native:
+            dev = host[:need].to(self.device, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            ring['events'][k] = ev
+            hip_ops.jpeg_pixels_bgr(dev[dbytes:].view(torch.int16), dev[:dbytes], out, slot)
+        for i, img in enumerate(host_imgs):
+            if img is not None:
+                out[i].copy_(torch.from_numpy(img))
+        return out
+
 
 @DATASETS.register_module()
 class CityscapesDataset(CocoDataset):
@@ -253,6 +325,103 @@ class CityscapesDataset(CocoDataset):
     @staticmethod
     def _degenerate(ann, img_info, x1, y1, w, h):
         return ann['area'] <= 0 or w < 1 or h < 1
+
+
+@DATASETS.register_module()
+class XMLDataset(CocoDataset):
+    """xml_style.py:14-154: VOC-style ``ann_file`` (one image id per line), ``{img_prefix}/{ann_subdir}/{id}.xml``
+    annotations and ``{img_subdir}/{id}.jpg`` images.  Each XML file is parsed once, here, instead of on every
+    ``_filter_imgs`` / ``get_ann_info`` call (same results).  Decoding, rings, ``batch()`` and ``flag`` are CocoDataset's."""
+
+    def __init__(self, min_size=None, img_subdir='JPEGImages', ann_subdir='Annotations', **kwargs):
+        assert self.CLASSES or kwargs.get('classes', None), 'CLASSES in `XMLDataset` can not be None.'
+        self.img_subdir, self.ann_subdir = img_subdir, ann_subdir
+        super().__init__(**kwargs)
+        self.cat2label = {cat: i for i, cat in enumerate(self.CLASSES)}
+        self.min_size = min_size
+
+    # ---- xml_style.py:38-67
+    def load_annotations(self, ann_file):
+        with open(ann_file) as f:
+            img_ids = [line.rstrip('\n\r') for line in f]          # mmcv.list_from_file
+        data_infos = []
+        for img_id in img_ids:
+            filename = os.path.join(self.img_subdir, f'{img_id}.jpg')
+            root = ET.parse(os.path.join(self.img_prefix, self.ann_subdir, f'{img_id}.xml')).getroot()
+            size = root.find('size')
+            if size is not None:
+                width, height = int(size.find('width').text), int(size.find('height').text)
+            else:
+                from PIL import Image
+                with Image.open(os.path.join(self.img_prefix, filename)) as img:
+                    width, height = img.size
+            objects = []
+            for obj in root.findall('object'):
+                difficult = obj.find('difficult')
+                bnd = obj.find('bndbox')
+                box = None if bnd is None else \
+                    [int(float(bnd.find(t).text)) for t in ('xmin', 'ymin', 'xmax', 'ymax')]
+                objects.append((obj.find('name').text, 0 if difficult is None else int(difficult.text), box))
+            data_infos.append(dict(id=img_id, filename=filename, width=width, height=height, objects=objects))
+        return data_infos
+
+    # ---- xml_style.py:69-88
+    def _filter_imgs(self, min_size=32):
+        valid_inds = []
+        for i, img_info in enumerate(self.data_infos):
+            if min(img_info['width'], img_info['height']) < min_size:
+                continue
+            if self.filter_empty_gt:
+                if any(name in self.CLASSES for name, _, _ in img_info['objects']):
+                    valid_inds.append(i)
+            else:
+                valid_inds.append(i)
+        return valid_inds
+
+    # ---- xml_style.py:90-154
+    def get_ann_info(self, idx):
+        bboxes, labels, bboxes_ignore, labels_ignore = [], [], [], []
+        for name, difficult, bbox in self.data_infos[idx]['objects']:
+            if name not in self.CLASSES:
+                continue
+            label = self.cat2label[name]
+            ignore = False
+            if self.min_size:
+                assert not self.test_mode
+                if bbox[2] - bbox[0] < self.min_size or bbox[3] - bbox[1] < self.min_size:
+                    ignore = True
+            if difficult or ignore:
+                bboxes_ignore.append(bbox)
+                labels_ignore.append(label)
+            else:
+                bboxes.append(bbox)
+                labels.append(label)
+        if not bboxes:
+            bboxes, labels = np.zeros((0, 4)), np.zeros((0,))
+        else:
+            bboxes, labels = np.array(bboxes, ndmin=2) - 1, np.array(labels)
+        if not bboxes_ignore:
+            bboxes_ignore, labels_ignore = np.zeros((0, 4)), np.zeros((0,))
+        else:
+            bboxes_ignore, labels_ignore = np.array(bboxes_ignore, ndmin=2) - 1, np.array(labels_ignore)
+        return dict(bboxes=bboxes.astype(np.float32), labels=labels.astype(np.int64),
+                    bboxes_ignore=bboxes_ignore.astype(np.float32), labels_ignore=labels_ignore.astype(np.int64))
+
+
+@DATASETS.register_module()
+class SdgodDataset(XMLDataset):
+    """sdgod.py:12-29: the Diverse-Weather (S-DGOD) classes; the year is inferred from ``img_prefix``.  (Its VOC-protocol
+    ``evaluate`` is not restated yet.)"""
+    CLASSES = ('bus', 'bike', 'car', 'motor', 'person', 'rider', 'truck')
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        if 'VOC2007' in self.img_prefix:
+            self.year = 2007
+        elif 'VOC2012' in self.img_prefix:
+            self.year = 2012
+        else:
+            raise ValueError('Cannot infer dataset year from img_prefix')
 
 
 @DATASETS.register_module()
@@ -295,6 +464,9 @@ def build_dataset(cfg, default_args=None, synthetic_fallback=False):
         from .pipelines import SyntheticCityscapes
         print(f"[oadg] {cfg.get('ann_file')} not found: using SyntheticCityscapes in place of {cfg.get('type')}", flush=True)
         keep = {k: v for k, v in (default_args or {}).items() if k in ('seed', 'device', 'test_mode')}
+        cls = DATASETS.get(cfg.get('type')) if cfg.get('type') in DATASETS else None
+        if isinstance(cls, type) and issubclass(cls, XMLDataset):     # labels within the head of a 7-class DWD config
+            keep['num_classes'] = len(cfg.get('classes') or cls.CLASSES)
         return SyntheticCityscapes(pipeline=cfg.get('pipeline'), **keep)
     if cfg.get('type') == 'RepeatDataset':
         return RepeatDataset(build_dataset(cfg['dataset'], default_args, synthetic_fallback), cfg['times'])

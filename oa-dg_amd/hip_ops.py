@@ -661,3 +661,30 @@ def nms_sorted_batched(boxes, counts, iou_thr, max_keep=-1):
     check(L.oadg_nms_batched(ptr(boxes), ptr(counts), n_img, Mmax, float(iou_thr), int(max_keep),
                              ptr(ws), nbytes, ptr(keep), ptr(keep_cnt), stream_ptr()), 'oadg_nms_batched')
     return keep, keep_cnt
+
+
+JPEG_DESC_BYTES = 672      # sizeof(oadg_jpeg_desc), include/oadg_hip.h
+
+
+def jpeg_pixels_bgr(coef, desc, out, slot, planes=None):
+    """Pixel stage of the JPEG decoder (csrc/jpeg_decode.hip) on torch's current stream: quantized coefficients from
+    ``oadg_jpeg_entropy_decode`` -> BGR uint8 ``out`` [n, H, W, 3].
+
+    coef: int16 device tensor, image i's slot at i * ``slot`` elements; desc: uint8 device tensor of n descriptors
+    (n * JPEG_DESC_BYTES, 16-byte aligned); planes: optional uint8 workspace of n * slot bytes.  Images whose descriptor
+    has ncomp 0 are left as they are in ``out``."""
+    require_cuda(coef, desc, out, planes)
+    n, H, W, C = out.shape
+    if C != 3 or out.dtype != torch.uint8 or not out.is_contiguous():
+        raise ValueError('out must be a contiguous uint8 [n, H, W, 3] tensor')
+    if coef.dtype != torch.int16 or coef.numel() < n * slot or desc.numel() < n * JPEG_DESC_BYTES:
+        raise ValueError('coef / desc do not cover the batch')
+    if desc.data_ptr() % 16 or coef.data_ptr() % 16:
+        raise ValueError('coef and desc must be 16-byte aligned')
+    if planes is None:
+        planes = torch.empty(n * slot, dtype=torch.uint8, device=out.device)
+    elif planes.numel() < n * slot:
+        raise ValueError('planes workspace too small')
+    check(_lib.lib().oadg_jpeg_pixels_bgr(ptr(coef), ptr(desc), n, int(slot), ptr(planes), ptr(out), H, W, stream_ptr()),
+          'oadg_jpeg_pixels_bgr')
+    return out

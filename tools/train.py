@@ -8,8 +8,9 @@
 
 CONFIG may be one of this repo's configs (configs/oadg/*.py) or an unmodified reference config (its
 ``/ws/external/...`` bases are resolved against the tree the config lives in, or $OADG_CONFIG_ROOT).
-``CityscapesDataset`` / ``CocoDataset`` (COCO-format json + image files, oadg_amd/datasets.py) and
-``SyntheticCityscapes`` are built; a dataset whose annotation file is absent on this machine is replaced by the
+``CityscapesDataset`` / ``CocoDataset`` (COCO-format json + image files, oadg_amd/datasets.py), ``SdgodDataset`` /
+``XMLDataset`` (VOC-style id lists + XML annotations + JPEG frames: the Diverse-Weather benchmark,
+configs/oadg/faster_rcnn_r101_dc5_1x_dwd_oadg_sdgod.py) and ``SyntheticCityscapes`` are built; a dataset whose annotation file is absent on this machine is replaced by the
 synthetic Cityscapes-shaped source (with a notice) while its pipeline list is honoured.
 """
 import argparse
