@@ -380,6 +380,65 @@ int oadg_glass_shuffle_u8(uint8_t* img, int H, int W, int C, int delta, int iter
 int oadg_chamfer_l2_5x5(const uint8_t* src, int H, int W, float* dist);
 
 /* ------------------------------------------------------------------------------------------------
+ * Robustness-benchmark corruptions on the DEVICE (csrc/corrupt.hip): the deterministic filtering and resampling of
+ * nine names (gaussian_blur, glass_blur, defocus_blur, motion_blur, zoom_blur, snow, brightness, saturate,
+ * elastic_transform) on a resident uint8 [N][H][W][3] batch, byte-identical to pipelines/corrupt.py's numpy / scipy
+ * host path.  The random draws, the filter weights and the uint8 -> float tables (`lut`: 256 entries, lut64 = u8 / 255.
+ * in float64, lut32 = the host's float32 value of a byte) come from the host, computed there as the host path computes
+ * them.  Channel order is whatever the batch holds.
+ *   oadg_corrupt_correlate1d    scipy.ndimage.correlate1d with a SYMMETRIC kernel weights[2 radius + 1] along axis 0
+ *                               (H) or 1 (W) of [N][H][W][C]; src float64, or uint8 read through lut (src_u8 != 0);
+ *                               mode OADG_CORRUPT_NEAREST / _REFLECT / _MIRROR; dst float64, dst != src
+ *   oadg_corrupt_epilogue       float64 [n] -> uint8(clip(x, 0, 1) * 255) (_TO_U8_CLIP), uint8(x * 255) (_TO_U8), or
+ *                               float32(x * scale) (_TO_F32)
+ *   oadg_corrupt_defocus        scipy.ndimage.correlate(mode='mirror') of each channel of lut64[src] with a 2-D
+ *                               footprint: taps dydx [ntaps][2] (offsets from the centre, row-major kernel order, the
+ *                               taps with |w| > DBL_EPSILON), weights [ntaps]; then uint8(clip * 255)
+ *   oadg_corrupt_zoom_blur      zoom_blur: per factor z, ratios [nz][2] = (ry, rx) of scipy's order-1 zoom and geo [nz][4]
+ *                               = (top, left, ch, cw) of the centre crop; the zoomed crops (float32, top-left trimmed)
+ *                               summed in order, (x + sum) / (nz + 1), uint8(clip * 255); lut = float32(u8 / 255.)
+ *   oadg_corrupt_snow_layer     snow's float64 layer src [N][h][w]: order-1 zoom of its crop (top, left, ch, cw) to
+ *                               dst [N][Ho][Wo], values < thresh set to 0, clipped to [0, 1]
+ *   oadg_corrupt_motion_blur_u8 / _f64   the package's motion blur: dst = sum_j kernel[j] * shift(src, dx_j, dy_j) in
+ *                               float64, in order, with taps [N][T][2] = (dx, dy) per image and counts [N] the taps
+ *                               before the early break; _u8: uint8 [N][H][W][3] in, uint8(clip(., 0, 255)) out; _f64:
+ *                               float64 [N][H][W] in, uint8(round(. * 255)) out
+ *   oadg_corrupt_snow_blend     snow's blend of src [N][h][w][3] with the blurred layer [N][Ho][Wo] (uint8) and its
+ *                               180-degree rotation; c6, one_minus_c6 the float32 values of c6 and 1 - c6
+ *   oadg_corrupt_elastic        scipy.ndimage.map_coordinates(order=1, mode='reflect') of lut32[src] at (y + dy, x + dx),
+ *                               dx, dy float32 [N][H][W]; uint8(clip * 255)
+ *   oadg_corrupt_hsv            brightness (which OADG_CORRUPT_BRIGHTNESS: v = clip(v + a, 0, 1)) or saturate
+ *                               (OADG_CORRUPT_SATURATE: s = clip(s * a + b, 0, 1)) through skimage's rgb2hsv / hsv2rgb,
+ *                               npix pixels of 3 channels */
+#define OADG_CORRUPT_NEAREST 0
+#define OADG_CORRUPT_REFLECT 1
+#define OADG_CORRUPT_MIRROR 2
+#define OADG_CORRUPT_TO_U8_CLIP 0
+#define OADG_CORRUPT_TO_U8 1
+#define OADG_CORRUPT_TO_F32 2
+#define OADG_CORRUPT_BRIGHTNESS 0
+#define OADG_CORRUPT_SATURATE 1
+int oadg_corrupt_correlate1d(const void* src, int src_u8, const double* lut, double* dst, int N, int H, int W, int C,
+                             int axis, const double* weights, int radius, int mode, void* stream);
+int oadg_corrupt_epilogue(const double* src, void* dst, long n, int kind, double scale, void* stream);
+int oadg_corrupt_defocus(const uint8_t* src, uint8_t* dst, int N, int H, int W, const int32_t* dydx,
+                         const double* weights, int ntaps, const double* lut, void* stream);
+int oadg_corrupt_zoom_blur(const uint8_t* src, uint8_t* dst, int N, int H, int W, const double* ratios,
+                           const int32_t* geo, int nz, const float* lut, void* stream);
+int oadg_corrupt_snow_layer(const double* src, double* dst, int N, int h, int w, int top, int left, int ch, int cw,
+                            int Ho, int Wo, double ry, double rx, double thresh, void* stream);
+int oadg_corrupt_motion_blur_u8(const uint8_t* src, uint8_t* dst, int N, int H, int W, const int32_t* taps,
+                                const int32_t* counts, const double* kernel, int T, void* stream);
+int oadg_corrupt_motion_blur_f64(const double* src, uint8_t* dst, int N, int H, int W, const int32_t* taps,
+                                 const int32_t* counts, const double* kernel, int T, void* stream);
+int oadg_corrupt_snow_blend(const uint8_t* src, const uint8_t* layer, uint8_t* dst, int N, int h, int w, int Ho, int Wo,
+                            float c6, float one_minus_c6, const float* lut32, const double* lut64, void* stream);
+int oadg_corrupt_elastic(const uint8_t* src, const float* dx, const float* dy, uint8_t* dst, int N, int H, int W,
+                         const float* lut, void* stream);
+int oadg_corrupt_hsv(const uint8_t* src, uint8_t* dst, long npix, int which, double a, double b, const double* lut,
+                     void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Geometric pipeline steps in front of OA-Mix on uint8 HWC images
  *   oadg_resize_bilinear_u8  Resize._resize_img  mmdet/datasets/pipelines/transforms.py:210-239
  *                            (mmcv.imrescale / imresize -> cv2.resize INTER_LINEAR, 8-bit fixed-point path)

@@ -173,6 +173,16 @@ SIGNATURES = {
     'oadg_jpeg_decode_bgr': (ci, [c_char_p, vp, ci, ci]),
     'oadg_glass_shuffle_u8': (ci, [vp, ci, ci, ci, ci, ci, vp]),
     'oadg_chamfer_l2_5x5': (ci, [vp, ci, ci, vp]),
+    'oadg_corrupt_correlate1d': (ci, [vp, ci, vp, vp, ci, ci, ci, ci, ci, vp, ci, ci, vp]),
+    'oadg_corrupt_epilogue': (ci, [vp, vp, cl, ci, cd, vp]),
+    'oadg_corrupt_defocus': (ci, [vp, vp, ci, ci, ci, vp, vp, ci, vp, vp]),
+    'oadg_corrupt_zoom_blur': (ci, [vp, vp, ci, ci, ci, vp, vp, ci, vp, vp]),
+    'oadg_corrupt_snow_layer': (ci, [vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, cd, cd, cd, vp]),
+    'oadg_corrupt_motion_blur_u8': (ci, [vp, vp, ci, ci, ci, vp, vp, vp, ci, vp]),
+    'oadg_corrupt_motion_blur_f64': (ci, [vp, vp, ci, ci, ci, vp, vp, vp, ci, vp]),
+    'oadg_corrupt_snow_blend': (ci, [vp, vp, vp, ci, ci, ci, ci, ci, cf, cf, vp, vp, vp]),
+    'oadg_corrupt_elastic': (ci, [vp, vp, vp, vp, ci, ci, ci, vp, vp]),
+    'oadg_corrupt_hsv': (ci, [vp, vp, cl, ci, cd, cd, vp, vp]),
     'oadg_oamix_compose': (ci, [vp, vp, ci, ci, POINTER(RegionOp), POINTER(ci), ci, vp, vp, vp, vp, cf, ci, vp]),
     'oadg_oamix_final': (ci, [vp, vp, ci, ci, vp, ci, vp, vp, cd, POINTER(cf), POINTER(cf), ci, vp, vp, ci, ci,
                               ci, vp]),

@@ -688,3 +688,141 @@ def jpeg_pixels_bgr(coef, desc, out, slot, planes=None):
     check(_lib.lib().oadg_jpeg_pixels_bgr(ptr(coef), ptr(desc), n, int(slot), ptr(planes), ptr(out), H, W, stream_ptr()),
           'oadg_jpeg_pixels_bgr')
     return out
+
+
+# --------------------------------------------------------------------------------------- robustness-benchmark corruptions
+# csrc/corrupt.hip: the device half of pipelines/corrupt.py's Corrupt.batch (pipelines/corrupt_device.py builds the
+# draws, weights and tables on the host and calls these on torch's current stream)
+CORRUPT_MODES = dict(nearest=0, reflect=1, mirror=2)
+CORRUPT_TO_U8_CLIP, CORRUPT_TO_U8, CORRUPT_TO_F32 = 0, 1, 2
+
+
+def _dense(t, dtype, what):
+    if t.dtype != dtype or not t.is_contiguous():
+        raise ValueError(f'{what} must be a contiguous {dtype} tensor')
+
+
+def _batch_u8(*ts):
+    for t in ts:
+        _dense(t, torch.uint8, 'image batch')
+        if t.dim() != 4 or t.shape[3] != 3:
+            raise ValueError('image batch must be uint8 [N, H, W, 3]')
+
+
+def corrupt_correlate1d(src, dst, axis, weights, mode, lut=None):
+    """scipy correlate1d (symmetric ``weights``, float64) along axis 0 (H) or 1 (W) of [N, H, W, C]: ``src`` float64, or
+    uint8 read as ``lut[src]``; ``dst`` float64 of the same shape"""
+    require_cuda(src, dst, weights, lut)
+    _dense(dst, torch.float64, 'dst')
+    _dense(weights, torch.float64, 'weights')
+    if src.dtype == torch.uint8:
+        _dense(lut, torch.float64, 'lut')
+    else:
+        _dense(src, torch.float64, 'src')
+    if src.shape != dst.shape or src.dim() != 4 or weights.numel() % 2 != 1:
+        raise ValueError('src / dst must be [N, H, W, C] alike and weights of odd length')
+    N, H, W, C = src.shape
+    check(_lib.lib().oadg_corrupt_correlate1d(ptr(src), int(src.dtype == torch.uint8), ptr(lut), ptr(dst), N, H, W, C,
+                                              int(axis), ptr(weights), weights.numel() // 2, CORRUPT_MODES[mode],
+                                              stream_ptr()), 'oadg_corrupt_correlate1d')
+
+
+def corrupt_epilogue(src, dst, kind, scale=1.0):
+    """float64 -> uint8(clip(x, 0, 1) * 255) / uint8(x * 255) / float32(x * scale), element by element"""
+    require_cuda(src, dst)
+    _dense(src, torch.float64, 'src')
+    _dense(dst, torch.float32 if kind == CORRUPT_TO_F32 else torch.uint8, 'dst')
+    if dst.numel() != src.numel():
+        raise ValueError('src / dst sizes differ')
+    check(_lib.lib().oadg_corrupt_epilogue(ptr(src), ptr(dst), src.numel(), int(kind), float(scale), stream_ptr()),
+          'oadg_corrupt_epilogue')
+
+
+def corrupt_defocus(src, dst, dydx, weights, lut64):
+    require_cuda(src, dst, dydx, weights, lut64)
+    _batch_u8(src, dst)
+    _dense(dydx, torch.int32, 'dydx')
+    _dense(weights, torch.float64, 'weights')
+    if dydx.numel() != 2 * weights.numel():
+        raise ValueError('dydx must be [ntaps, 2]')
+    N, H, W, _ = src.shape
+    check(_lib.lib().oadg_corrupt_defocus(ptr(src), ptr(dst), N, H, W, ptr(dydx), ptr(weights), weights.numel(),
+                                          ptr(lut64), stream_ptr()), 'oadg_corrupt_defocus')
+
+
+def corrupt_zoom_blur(src, dst, ratios, geo, lut32):
+    require_cuda(src, dst, ratios, geo, lut32)
+    _batch_u8(src, dst)
+    _dense(ratios, torch.float64, 'ratios')
+    _dense(geo, torch.int32, 'geo')
+    nz = ratios.numel() // 2
+    if ratios.numel() != 2 * nz or geo.numel() != 4 * nz:
+        raise ValueError('ratios [nz, 2] and geo [nz, 4] expected')
+    N, H, W, _ = src.shape
+    check(_lib.lib().oadg_corrupt_zoom_blur(ptr(src), ptr(dst), N, H, W, ptr(ratios), ptr(geo), nz, ptr(lut32),
+                                            stream_ptr()), 'oadg_corrupt_zoom_blur')
+
+
+def corrupt_snow_layer(src, dst, crop, ratios, thresh):
+    """src float64 [N, h, w] -> dst float64 [N, Ho, Wo]; crop = (top, left, ch, cw), ratios = (ry, rx)"""
+    require_cuda(src, dst)
+    _dense(src, torch.float64, 'src')
+    _dense(dst, torch.float64, 'dst')
+    N, h, w = src.shape
+    Ho, Wo = dst.shape[1:]
+    check(_lib.lib().oadg_corrupt_snow_layer(ptr(src), ptr(dst), N, h, w, *[int(v) for v in crop], Ho, Wo,
+                                             float(ratios[0]), float(ratios[1]), float(thresh), stream_ptr()),
+          'oadg_corrupt_snow_layer')
+
+
+def corrupt_motion_blur(src, dst, taps, counts, kernel):
+    """uint8 [N, H, W, 3] -> uint8, or float64 [N, H, W] -> uint8 [N, H, W]; taps int32 [N, T, 2] = (dx, dy)"""
+    require_cuda(src, dst, taps, counts, kernel)
+    _dense(dst, torch.uint8, 'dst')
+    _dense(taps, torch.int32, 'taps')
+    _dense(counts, torch.int32, 'counts')
+    _dense(kernel, torch.float64, 'kernel')
+    T = kernel.numel()
+    if taps.numel() != 2 * T * counts.numel() or counts.numel() != src.shape[0]:
+        raise ValueError('taps must be [N, T, 2] and counts [N]')
+    if src.dtype == torch.uint8:
+        _batch_u8(src, dst)
+        fn, name = _lib.lib().oadg_corrupt_motion_blur_u8, 'oadg_corrupt_motion_blur_u8'
+    else:
+        _dense(src, torch.float64, 'src')
+        if src.dim() != 3 or dst.shape != src.shape:
+            raise ValueError('a float64 plane batch [N, H, W] and a uint8 dst alike expected')
+        fn, name = _lib.lib().oadg_corrupt_motion_blur_f64, 'oadg_corrupt_motion_blur_f64'
+    N, H, W = src.shape[:3]
+    check(fn(ptr(src), ptr(dst), N, H, W, ptr(taps), ptr(counts), ptr(kernel), T, stream_ptr()), name)
+
+
+def corrupt_snow_blend(src, layer, dst, c6, one_minus_c6, lut32, lut64):
+    require_cuda(src, layer, dst, lut32, lut64)
+    _batch_u8(src, dst)
+    _dense(layer, torch.uint8, 'layer')
+    N, h, w, _ = src.shape
+    Ho, Wo = layer.shape[1:]
+    check(_lib.lib().oadg_corrupt_snow_blend(ptr(src), ptr(layer), ptr(dst), N, h, w, Ho, Wo, float(c6),
+                                             float(one_minus_c6), ptr(lut32), ptr(lut64), stream_ptr()),
+          'oadg_corrupt_snow_blend')
+
+
+def corrupt_elastic(src, dx, dy, dst, lut32):
+    require_cuda(src, dx, dy, dst, lut32)
+    _batch_u8(src, dst)
+    _dense(dx, torch.float32, 'dx')
+    _dense(dy, torch.float32, 'dy')
+    N, H, W, _ = src.shape
+    if dx.shape != (N, H, W) or dy.shape != (N, H, W):
+        raise ValueError('dx / dy must be float32 [N, H, W]')
+    check(_lib.lib().oadg_corrupt_elastic(ptr(src), ptr(dx), ptr(dy), ptr(dst), N, H, W, ptr(lut32), stream_ptr()),
+          'oadg_corrupt_elastic')
+
+
+def corrupt_hsv(src, dst, which, a, b, lut64):
+    """brightness (which 0: v = clip(v + a, 0, 1)) or saturate (which 1: s = clip(s * a + b, 0, 1))"""
+    require_cuda(src, dst, lut64)
+    _batch_u8(src, dst)
+    check(_lib.lib().oadg_corrupt_hsv(ptr(src), ptr(dst), src.numel() // 3, int(which), float(a), float(b), ptr(lut64),
+                                      stream_ptr()), 'oadg_corrupt_hsv')

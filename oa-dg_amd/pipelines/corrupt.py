@@ -22,8 +22,10 @@ PARITY UNPINNED: no copy of the package exists to compare with; tests/test_corru
 impulse images, the chamfer transform and the shuffle against plain-Python loops, Canny on synthetic edges) and the
 statistics of the noise models.  Random draws come from numpy's global stream, as in the package - except glass_blur's
 offsets, which the package draws from numba's private generator inside its compiled loop (no stream to replay).
-Evaluation-time host code (the reference corrupts numpy images inside its DataLoader workers too); it is not part of the
-training hot path.
+Evaluation-time code (the reference corrupts numpy images inside its DataLoader workers too); it is not part of the
+training hot path.  ``Corrupt.batch`` of a batch resident on the GPU runs the names of ``DEVICE_CORRUPTIONS`` on the device
+(pipelines/corrupt_device.py, csrc/corrupt.hip: the same bytes and the same draws from numpy's stream); the other names,
+CPU batches, ``Corrupt.__call__`` and every batch when ``OADG_DEVICE_CORRUPT=0`` run on the host.
 """
 import math
 import os
@@ -37,6 +39,13 @@ IMPLEMENTED = ('gaussian_noise', 'shot_noise', 'impulse_noise', 'defocus_blur', 
                'snow', 'frost', 'fog', 'brightness', 'contrast', 'elastic_transform', 'pixelate', 'jpeg_compression',
                'speckle_noise', 'gaussian_blur', 'spatter', 'saturate')
 NEEDS_ASSETS = ('frost',)          # runs when OADG_FROST_DIR holds the package's six frost photographs
+# Corrupt.batch on a GPU batch: these run on the device (byte-identical), the others stay on the host - shot_noise (its
+# Poisson draws depend on the pixels), pixelate and jpeg_compression (Pillow), spatter (connected components), frost
+# (photographs), the noise models, contrast and fog
+DEVICE_CORRUPTIONS = ('gaussian_blur', 'glass_blur', 'defocus_blur', 'motion_blur', 'zoom_blur', 'snow', 'brightness',
+                      'saturate', 'elastic_transform')
+HOST_CORRUPTIONS = ('gaussian_noise', 'shot_noise', 'impulse_noise', 'speckle_noise', 'contrast', 'fog', 'pixelate',
+                    'jpeg_compression', 'spatter', 'frost')
 
 
 def _rgb2hsv(x):
@@ -293,17 +302,24 @@ def _motion_kernel(radius, sigma):
     return k / np.sum(k)
 
 
-def _motion_blur(x, radius, sigma, angle):
-    kernel = _motion_kernel(radius, sigma)
-    width = kernel.shape[0]
+def _motion_taps(shape, width, angle):
+    """the (dx, dy) shifts of the motion blur's steps, up to the first one that leaves an image of ``shape``"""
     point = (width * np.sin(np.deg2rad(angle)), width * np.cos(np.deg2rad(angle)))
     hypot = math.hypot(point[0], point[1])
-    blurred = np.zeros_like(x, dtype=np.float32)
+    taps = []
     for i in range(width):
         dy = -math.ceil(((i * point[0]) / hypot) - 0.5)
         dx = -math.ceil(((i * point[1]) / hypot) - 0.5)
-        if abs(dy) >= x.shape[0] or abs(dx) >= x.shape[1]:
+        if abs(dy) >= shape[0] or abs(dx) >= shape[1]:
             break                       # the simulated motion left the image
+        taps.append((dx, dy))
+    return taps
+
+
+def _motion_blur(x, radius, sigma, angle):
+    kernel = _motion_kernel(radius, sigma)
+    blurred = np.zeros_like(x, dtype=np.float32)
+    for i, (dx, dy) in enumerate(_motion_taps(x.shape, kernel.shape[0], angle)):
         blurred = blurred + kernel[i] * _shift(x, dx, dy)
     return blurred
 
@@ -510,6 +526,8 @@ class Corrupt:
     """transforms.py:1277-1317; accepts the results dict of the reference (numpy ``img``) and, for the device pipeline, a
     uint8 [N, H, W, 3] batch through :meth:`batch`."""
 
+    runs = dict(device=0, host=0)       # images corrupted by :meth:`batch` on the device / on the host (all instances)
+
     def __init__(self, corruption, severity=1):
         self.corruption, self.severity = corruption, severity
 
@@ -520,10 +538,20 @@ class Corrupt:
         return results
 
     def batch(self, imgs_u8):
-        """a resident uint8 batch: corrupted on the host image by image (as the reference's workers do) and uploaded again"""
+        """a resident uint8 batch.  On the GPU, a name of DEVICE_CORRUPTIONS is corrupted there (pipelines/corrupt_device.py,
+        byte for byte and draw for draw as below) unless OADG_DEVICE_CORRUPT=0; otherwise it is corrupted on the host image
+        by image (as the reference's workers do) and uploaded again"""
         import torch
+        n = int(imgs_u8.shape[0])
+        if imgs_u8.is_cuda and self.corruption in DEVICE_CORRUPTIONS and self.severity != 0 and \
+                os.environ.get('OADG_DEVICE_CORRUPT', '1') != '0':
+            from .corrupt_device import corrupt_batch
+            out = corrupt_batch(imgs_u8, self.corruption, self.severity)
+            Corrupt.runs['device'] += n
+            return out
         host = imgs_u8.cpu().numpy()
         out = np.stack([corrupt(im, self.corruption, self.severity) for im in host])
+        Corrupt.runs['host'] += n
         return torch.from_numpy(out).to(imgs_u8.device)
 
     def __repr__(self):
