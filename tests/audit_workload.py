@@ -64,3 +64,54 @@ def audited_step(dev, monkeypatch, cfg_path, batch, H, W, boxes, classes, box_si
         return out, det, wall
     finally:
         hip_conv.enable(False)
+
+
+def tta_pipeline(img_scale, flip=False):
+    """the reference's Cityscapes / DWD test pipeline (MultiScaleFlipAug over Resize(keep_ratio) ... Pad(32))"""
+    norm = dict(mean=[123.675, 116.28, 103.53], std=[58.395, 57.12, 57.375], to_rgb=True)
+    inner = [dict(type='Resize', keep_ratio=True), dict(type='RandomFlip'), dict(type='Normalize', **norm),
+             dict(type='Pad', size_divisor=32), dict(type='ImageToTensor', keys=['img']), dict(type='Collect', keys=['img'])]
+    return [dict(type='LoadImageFromFile'), dict(type='MultiScaleFlipAug', img_scale=img_scale, flip=flip, transforms=inner)]
+
+
+def audited_inference(dev, monkeypatch, tmp_path, cfg_path, batch, H, W, install, pipeline=None, on_forward=None):
+    """(results of the two forwards, model, wall seconds of each) of bf16 test-time inference as tools/test.py runs it:
+    build_model on a checkpoint file of deterministic weights (tests/golden/inputs.py named_weights), batches of the test
+    pipeline (DevicePipeline.test_batch; ``pipeline`` overrides the config's), ``model(return_loss=False, rescale=True)``
+    under no_grad and bf16 autocast.  ``install(monkeypatch, model)`` wraps the entry points before the first forward (cold:
+    the weight preparation launches) and stays installed for the second (served from the bank); ``on_forward(k, model,
+    results, data)`` runs after forward k (0, 1) with the batch it ran on."""
+    from inputs import named_weights
+    from oadg_amd import Config, build_detector, hip_conv
+    from oadg_amd.apis import set_random_seed
+    from oadg_amd.pipelines import DevicePipeline, SyntheticCityscapes
+    from test_cli import _load
+    test_tool = _load('test')
+    cfg = Config.fromfile(cfg_path)
+    ck = str(tmp_path / 'weights.pth')
+    try:
+        set_random_seed(0)
+        shapes = {k: v.shape for k, v in build_detector(Config.fromfile(cfg_path).model).state_dict().items()}
+        torch.save({'state_dict': {k: torch.as_tensor(v) for k, v in named_weights(shapes).items()}}, ck)
+        model = test_tool.build_model(cfg, ck, dev, torch.bfloat16)
+        assert hip_conv.ENABLED and not model.training
+        pipe = DevicePipeline(pipeline if pipeline is not None else cfg.data.test.pipeline, dtype=torch.bfloat16)
+        ds = SyntheticCityscapes(img_shape=(H, W), num_boxes=12, box_size=(24, 300), seed=3, device=dev)
+        imgs, _, _ = ds.batch(list(range(batch)))
+        install(monkeypatch, model)
+        outs, walls = [], []
+        for k in range(2):
+            data = pipe.test_batch(imgs)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            with torch.no_grad(), torch.autocast('cuda', dtype=torch.bfloat16):
+                res = model(return_loss=False, rescale=True, **data)
+            torch.cuda.synchronize()
+            walls.append(time.perf_counter() - t0)
+            outs.append(res)
+            if on_forward is not None:
+                on_forward(k, model, res, data)
+        monkeypatch.undo()
+        return outs, model, walls
+    finally:
+        hip_conv.enable(False)

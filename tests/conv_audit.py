@@ -534,7 +534,9 @@ class Auditor:
             y = bm(x, bias)
             sync()
             with torch.no_grad():
-                t = x.detach().double() + (bias.detach().double().view(1, -1, 1, 1) if bias is not None else 0)
+                # csrc bias_relu_maxpool_kernel casts the bias to bf16 as autocast would (`bf16_to_f32(f32_to_bf16(bias))`):
+                # the operand the sum receives
+                t = x.detach().double() + (bf16(bias.detach().double()).view(1, -1, 1, 1) if bias is not None else 0)
                 r = F.max_pool2d(t.clamp_min(0), 3, 2, 1)
                 A.record('bias_relu_maxpool_kernel', x.shape, _nhwc64(y), _nhwc64(r), bound(_nhwc64(r), 0, RHO))
             return y

@@ -1209,3 +1209,52 @@ def test_fpn_topdown_add_in_the_lateral_epilogue_is_bit_identical(dev, monkeypat
         assert torch.equal(a, b)
     for n_ in res[False][2]:
         assert torch.equal(res[True][2][n_], res[False][2][n_]), n_
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('scales', [[8], [2, 4, 8, 16, 32]])
+def test_rpn_head_outputs_at_test_time_stay_on_the_mfma_kernel(dev, monkeypatch, scales):
+    """Under no_grad (tools/test.py) rpn_cls / rpn_reg (3 + 12 or 15 + 60 output channels) run as the zero-padded 1x1
+    convolution of the training path, never F.conv2d (whose bf16 result is up to 2.7 roundings from the fp32 sum): every
+    output element within one bf16 rounding of the fp64 convolution of the rpn_conv output it received."""
+    import conv_audit as CA
+    from oadg_amd import dense_heads, hip_conv
+    from oadg_amd.dense_heads import RPNHead
+    torch.manual_seed(0)
+    head = RPNHead(in_channels=256, feat_channels=256,
+                   anchor_generator=dict(type='AnchorGenerator', scales=scales, ratios=[0.5, 1.0, 2.0], strides=[4]),
+                   loss_cls=dict(type='CrossEntropyLoss', use_sigmoid=True, loss_weight=1.0),
+                   loss_bbox=dict(type='L1Loss', loss_weight=1.0)).to(dev)
+    for m in (head.rpn_conv, head.rpn_cls, head.rpn_reg):
+        torch.nn.init.normal_(m.weight, 0, 0.05)
+        torch.nn.init.normal_(m.bias, 0, 0.1)
+    x = torch.randn(2, 256, 40, 56, device=dev).contiguous(memory_format=torch.channels_last)
+    seen = []
+    conv = dense_heads.conv2d
+
+    def spy(x_, w, b, *a, **k):
+        y = conv(x_, w, b, *a, **k)
+        seen.append((x_, w, b, y))
+        return y
+
+    def library(*a, **k):
+        raise AssertionError('a test-time RPN head convolution reached F.conv2d')
+    monkeypatch.setattr(dense_heads, 'conv2d', spy)
+    monkeypatch.setattr(torch.nn.functional, 'conv2d', library)
+    hip_conv.enable()
+    try:
+        with torch.no_grad(), torch.autocast('cuda', dtype=torch.bfloat16):
+            cls, reg = head.forward_single(x)
+    finally:
+        hip_conv.enable(False)
+    n_cls, n_reg = head.rpn_cls.out_channels, head.rpn_reg.out_channels
+    assert cls.shape == (2, n_cls, 40, 56) and reg.shape == (2, n_reg, 40, 56) and len(seen) == 2
+    h, w, b, y = seen[1]
+    assert tuple(w.shape) == (128, 256, 1, 1) and y.dtype == torch.bfloat16
+    with torch.no_grad():
+        # the kernel's operands: the prepared bf16 weight, the fp32 bias
+        r, bd = CA.forward_expect(h, w.to(torch.bfloat16), b, None, 1, 0, 1, False)
+        o = CA._nhwc64(torch.cat([cls, reg], 1))
+        assert CA.ratio(o, r[..., :n_cls + n_reg], bd[..., :n_cls + n_reg])[0] <= 1.0
+        assert torch.equal(w[:n_cls], head.rpn_cls.weight) and torch.equal(w[n_cls:n_cls + n_reg], head.rpn_reg.weight)
+        assert not w[n_cls + n_reg:].any() and torch.equal(b[:n_cls], head.rpn_cls.bias)

@@ -77,7 +77,7 @@ def test_simple_test_host_logic_vs_reference(golden_dir, monkeypatch):
 
 @pytest.mark.gpu
 def test_simple_test_on_gpu_close_to_reference(dev, golden_dir, monkeypatch):
-    """fp32 product path (HIP RoIAlign / NMS, MIOpen convs): discrete NMS decisions may flip on ulp differences, so
+    """fp32 product path (HIP RoIAlign / NMS, fp32 MFMA convolutions of csrc/conv_f32.hip): discrete NMS decisions may flip on ulp differences, so
     the bar is the detection count per class within 5 and the top-scored boxes matching to 1e-2."""
     monkeypatch.setattr(torch.backends.cudnn, 'deterministic', True)
     g = np.load(os.path.join(golden_dir, 'model_test_256x512.npz'))

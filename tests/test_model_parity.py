@@ -4,7 +4,7 @@ REFERENCE FasterRCNN+ContrastiveRoIHead train step (tests/golden/make_golden_mod
 * CPU (not gpu): our host logic (anchors, assign, sample, targets, random proposals, list plumbing, module
   layout / state_dict names) with the four HIP entry points swapped for the oracle -> must reproduce the
   reference's losses, sampled labels and gradient norms essentially exactly.
-* GPU: the product path (HIP losses / RoIAlign / NMS, torch fp32 convs) on the same inputs.
+* GPU: the product path (HIP losses / RoIAlign / NMS, fp32 MFMA convolutions of csrc/conv_f32.hip) on the same inputs.
 """
 import os
 
@@ -100,16 +100,16 @@ def test_host_logic_reproduces_reference_step(golden_dir, fold_bn, monkeypatch):
 
 @pytest.mark.gpu
 def test_product_step_matches_reference_on_gpu(dev, golden_dir, monkeypatch):
-    """fp32 on the MI355X.  Convolutions come from a different library (MIOpen vs the CPU's oneDNN), and the
+    """fp32 on the MI355X.  Convolutions come from a different implementation (csrc/conv_f32.hip vs the CPU's oneDNN), and the
     step contains discrete decisions (top-k, NMS, IoU thresholds, sampling): measured (round 3) 1e-7 on the RPN
     terms, 3.3e-4 on loss_cls, 9e-5 on loss_cont, 2e-3 on acc; asserted at 1e-3 (acc 1e-2) and 1e-3 for the
     gradient norms - about 3x the measured deviations; the 1e-4 bar is held by the per-kernel tests, which feed
     identical inputs to both sides."""
     g = np.load(os.path.join(golden_dir, 'model_step_256x512.npz'))
     torch.backends.cudnn.allow_tf32 = False
-    # MIOpen's default fp32 solvers reduce split-K partials with atomics: ulp-level run-to-run noise that flips a
-    # discrete decision (NMS / top-k) about once in 15 runs and with it the whole RoI sample.  Deterministic
-    # solvers make the step reproducible (tools/probe/nondet_probe.py: 40/40 identical).
+    # The convolutions run on csrc/conv_f32.hip, whose split partials are summed in a fixed order; the flag still pins
+    # MIOpen's solvers for whatever library convolution remains (atomic split-K reductions there give ulp-level run-to-run
+    # noise that can flip a discrete decision - NMS / top-k - and with it the whole RoI sample).
     monkeypatch.setattr(torch.backends.cudnn, 'deterministic', True)
     det = build_and_load(dev)
     data = make_data(g, dev)
