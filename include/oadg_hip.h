@@ -844,7 +844,7 @@ typedef struct oadg_roi_sample_image {
     int n;
 } oadg_roi_sample_image;
 int oadg_roi_sample_max_rows(void);
-int oadg_roi_sample_device(const oadg_roi_sample_image* images_host, int B, int num, int num_pos_exp, float neg_pos_ub,
+int oadg_roi_sample_device(const oadg_roi_sample_image* images_host, int B, int num, int num_pos_exp, double neg_pos_ub,
                            const uint32_t* mt_state, uint32_t* mt_state_out, int64_t* sel, int* counts, int* flags,
                            void* stream);
 

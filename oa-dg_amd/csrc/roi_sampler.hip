@@ -31,7 +31,7 @@ struct RoiSampleArgs {
     const long long* gt[RS_MAX_IMAGES];
     int n[RS_MAX_IMAGES];
     int B, num, num_pos_exp;
-    float neg_pos_ub;
+    double neg_pos_ub;         // compared and multiplied in double, as the reference's Python expression is
     const unsigned* mt;        // [626]: state[624], left, next - read-only for the whole launch
     unsigned* mt_out;          // [626]: the advanced state (written by the last image's workgroup only)
     long long* sel;            // [B][num]
@@ -142,8 +142,10 @@ __global__ __launch_bounds__(256) void roi_sample_kernel(const RoiSampleArgs a) 
         np = cnt[j][0]; nn = cnt[j][1];
         kp = np < a.num_pos_exp ? np : a.num_pos_exp;
         int ne = a.num - kp;
-        if (a.neg_pos_ub >= 0.f) {
-            const int ub = (int)(a.neg_pos_ub * (float)(kp > 1 ? kp : 1));
+        if (a.neg_pos_ub >= 0.0) {
+            // int(neg_pos_ub * max(1, num_sampled_pos)) of base_sampler.py:91-95 is a Python (double) product: in fp32
+            // 0.29 * 100 rounds up to 29 where the reference truncates 28.999999999999996 to 28
+            const int ub = (int)(a.neg_pos_ub * (double)(kp > 1 ? kp : 1));
             ne = ne < ub ? ne : ub;
         }
         kn = nn < ne ? nn : ne;
@@ -245,7 +247,7 @@ __global__ __launch_bounds__(256) void roi_sample_kernel(const RoiSampleArgs a) 
 extern "C" int oadg_roi_sample_max_rows(void) { return RS_MAXN; }
 
 extern "C" int oadg_roi_sample_device(const oadg_roi_sample_image* images_host, int B, int num, int num_pos_exp,
-                                      float neg_pos_ub, const uint32_t* mt_state, uint32_t* mt_state_out, int64_t* sel,
+                                      double neg_pos_ub, const uint32_t* mt_state, uint32_t* mt_state_out, int64_t* sel,
                                       int* counts, int* flags, void* stream) {
     if (!images_host || B < 1 || B > RS_MAX_IMAGES || num < 1 || num_pos_exp < 0 || num_pos_exp > num || !mt_state ||
         !mt_state_out || mt_state_out == mt_state || !sel || !counts || !flags)

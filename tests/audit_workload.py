@@ -12,10 +12,11 @@ DC5_CFG = os.path.join(ROOT, 'configs', 'oadg', 'faster_rcnn_r101_dc5_1x_dwd_oad
 
 
 def audited_step(dev, monkeypatch, cfg_path, batch, H, W, boxes, classes, box_size, install, on_begin=None,
-                 on_end_backward=None, before_step1=None):
+                 on_end_backward=None, before_step1=None, speculative_sampling=None):
     """(out of the audited step, det, wall seconds).  ``install(monkeypatch, det)`` wraps the entry points after step 1;
     ``on_begin()`` / ``on_end_backward(det)`` run inside hip_conv.begin_step / end_backward of the audited step;
-    ``before_step1(monkeypatch, det)`` may wrap something for step 1 as well (it stays installed for step 2)."""
+    ``before_step1(monkeypatch, det)`` may wrap something for step 1 as well (it stays installed for step 2);
+    ``speculative_sampling`` (not None) sets TrainEngine.speculative_sampling - False: the RoI sampler draws on the host."""
     from oadg_amd import Config, build_detector, hip_conv
     from oadg_amd.apis import TrainEngine, build_optimizer, set_random_seed
     from oadg_amd.pipelines import DevicePipeline, SyntheticCityscapes
@@ -28,6 +29,8 @@ def audited_step(dev, monkeypatch, cfg_path, batch, H, W, boxes, classes, box_si
         det = det.to(dev).to(memory_format=torch.channels_last).train()
         det.log_vars_on_host = False
         engine = TrainEngine(det, build_optimizer(det, cfg.optimizer), amp_dtype=torch.bfloat16)
+        if speculative_sampling is not None:
+            engine.speculative_sampling = speculative_sampling
         set_random_seed(1)
         ds = SyntheticCityscapes(img_shape=(H, W), num_boxes=boxes, num_classes=classes, box_size=box_size, seed=0,
                                  device=dev)

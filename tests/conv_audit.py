@@ -25,6 +25,17 @@ RHO = 2.0 ** -8          # one bf16 rounding (8 significant bits, round to neare
 # margin of 3.6x.  (2^-20 would reject correct fp32 sums: that element needs 2^-15.85.)
 GAMMA = 2.0 ** -14
 ALPHA = 1e-30            # absolute floor (values that flush to zero as fp32 / bf16 denormals)
+# the C-ABI calls this auditor answers for (tests/test_target_audit.py's closure over the call sites of oa-dg_amd/): every
+# launch of hip_conv.py, the stem, the fused max-pool and the FPN top-down pair
+CLAIMS = {
+    'oadg_conv2d_nhwc_bf16_ex', 'oadg_conv2d_nhwc_bf16_scatter', 'oadg_conv2d_dgrad_s2_nhwc_bf16', 'oadg_conv2d_wgrad_nhwc_bf16',
+    'oadg_conv2d_wgrad_parts_nhwc_bf16', 'oadg_conv2d_wgrad_multi', 'oadg_colsum_reduce', 'oadg_colsum_reduce_multi',
+    'oadg_relu_bias_bwd', 'oadg_prep_conv_weights', 'oadg_prep_conv_weights_multi', 'oadg_prep_conv_weights_bwd',
+    'oadg_prep_conv_weights_bwd_parts', 'oadg_prep_conv_weights_bwd_parts_multi', 'oadg_bottleneck_frozen_256',
+    'oadg_bottleneck_frozen_first_64', 'oadg_conv1x1_n16_fwd', 'oadg_conv1x1_n16_dgrad', 'oadg_conv1x1_n16_wgrad',
+    'oadg_stem_conv7x7s2_nhwc_bf16',
+    'oadg_bias_relu_maxpool_nhwc_bf16', 'oadg_fpn_topdown_fwd', 'oadg_fpn_topdown_bwd',
+}
 
 
 # ---------------------------------------------------------------------------------------------------- fp64 references

@@ -44,6 +44,12 @@ TOL_LVL = 1e-5           # log2(sqrt(wh) / finest + 1e-6)
 GRID_ERR = 2.0 ** -21    # rh / PH (an adaptive sample count is ceil of it): see roi_geometry
 TOL_POS = 4 * POS_ERR    # a sample coordinate against -1 and the map size
 IGNORE_INDEX = -100
+# the C-ABI calls this auditor answers for (tests/test_target_audit.py's closure over the call sites of oa-dg_amd/)
+CLAIMS = {
+    'oadg_roi_align_fwd', 'oadg_roi_align_bwd', 'oadg_roi_align_bwd_tiles', 'oadg_roi_order', 'oadg_roi_order_keys',
+    'oadg_rpn_loss_fwd', 'oadg_rpn_loss_bwd', 'oadg_ce_jsd_fwd', 'oadg_ce_jsd_bwd', 'oadg_roi_reg_acc_fwd', 'oadg_roi_reg_bwd',
+    'oadg_supcon_fwd', 'oadg_supcon_bwd', 'oadg_parse_losses', 'oadg_fc_weight_permute', 'oadg_sgd_step_multi',
+}
 
 
 def bf16(t):

@@ -1,7 +1,8 @@
 """Launch auditor of the parts of bf16 test-time inference that no training audit checks: the fused RPN proposals and every
-NMS launch (a training step makes its RoI proposals on the same kernels, unaudited), the forward outputs of the RoI head's
-linears on autocast's casts, any convolution that reaches the library's F.conv2d (a row per layer shape - none is expected)
-and the detector's post-processing.  The MFMA convolutions, the weight preparation and RoIAlign of the same forward pass
+NMS launch (a training step makes its RoI proposals on the same kernels: tests/target_audit.py runs the same two wrappers
+there, at nms_pre = 2000 with padded lists), the forward outputs of the RoI head's linears on autocast's casts, any
+convolution that reaches the library's F.conv2d (a row per layer shape - none is expected) and the detector's
+post-processing.  The MFMA convolutions, the weight preparation and RoIAlign of the same forward pass
 are audited by tests/conv_audit.py and tests/head_audit.py, installed beside this one.
 
 Bounds in the form of tests/conv_audit.py (``|o - r| <= RHO |r| + GAMMA S + ALPHA``); exact operations are compared bit
@@ -215,21 +216,26 @@ def compare_detections(result, boxes, btol, scores, stol, score_thr, iou_thr, ma
 
 
 # ----------------------------------------------------------------------------------------------------------- auditor
-class Auditor(HA.Auditor):
-    """rows / failures / kernels / borderline as tests/head_audit.py's Auditor"""
+# the C-ABI calls this auditor answers for (tests/test_target_audit.py's closure over the call sites): the proposal and NMS
+# launches, at test-time settings here and at training settings through tests/target_audit.py
+CLAIMS = {'oadg_rpn_topk', 'oadg_rpn_decode', 'oadg_rpn_order', 'oadg_rpn_gather', 'oadg_nms_batched'}
 
-    def __init__(self):
-        super().__init__()
-        self.quiet = 0               # >0 while a reference path runs (its NMS launches are not the product's)
-        self.post = []               # per forward: the captured (rois, cls_score, bbox_pred, metas) of the RoI head
-        self.results = []            # per forward: what the detector returned
 
-    def install(self, mp, det):
+class ProposalAudit:
+    """the two wrappers of the RoI proposals, shared with tests/target_audit.py (the training step makes its proposals on
+    the same kernels): every NMS launch against oracle/nms.py, RPNHead.get_bboxes' fused path against its tensor path.
+    Needs ``self.quiet`` (> 0 while a reference path runs) beside tests/head_audit.py's Auditor."""
+
+    def after_proposals(self, head, cfg, padded, out, nms_counts):
+        """hook: the proposal lists ``out`` of one get_bboxes call and the kept counts of its NMS launch"""
+
+    def install_proposals(self, mp):
         from oadg_amd import _lib, dense_heads, hip_ops
         A = self
         sync = torch.cuda.synchronize
         launches = []
         chk = _lib.check
+        last_nms = []
 
         def check(rc, what):
             launches.append(what)
@@ -247,6 +253,7 @@ class Auditor(HA.Auditor):
             sync()
             with torch.no_grad():
                 A._check_nms(boxes, counts, iou_thr, max_keep, keep, cnt)
+            last_nms[:] = [cnt]
             return keep, cnt
         mp.setattr(hip_ops, 'nms_sorted_batched', nms_sorted_batched)
 
@@ -269,8 +276,50 @@ class Auditor(HA.Auditor):
                 A.quiet -= 1
             assert (head.FUSED_PROPOSALS, head.FUSED_TOPK) == saved
             A._check_proposals(ran, out, ref)
+            A.after_proposals(head, head.test_cfg if cfg is None else cfg, padded, out, last_nms[0] if last_nms else None)
             return out
         mp.setattr(dense_heads.RPNHead, 'get_bboxes', get_bboxes)
+        return self
+
+    def _check_nms(self, boxes, counts, iou_thr, max_keep, keep, cnt):
+        n_img, M = boxes.shape[:2]
+        mk = max_keep if 0 < max_keep <= M else M
+        words = (M + 63) // 64
+        self.kernels.add('nms_mask_kernel')
+        name = 'nms_scan_kernel<3, 2>' if words <= 64 * 3 else 'nms_scan_kernel<MAX_WORDS_PER_LANE, 1>'
+        c = counts.cpu().tolist()
+        k = cnt.cpu().tolist()
+        for i in range(n_img):
+            ref = nms_expect(boxes[i].float(), int(c[i]), float(iou_thr), mk)
+            got = keep[i, :int(k[i])].cpu().numpy().astype(np.int64)
+            self.exact(name, (n_img, M, int(c[i])), int(k[i]) == len(ref) and np.array_equal(got, ref), check='keep list')
+
+    def _check_proposals(self, ran, out, ref):
+        fused = 'oadg_rpn_gather' in ran
+        if fused:
+            self.kernels.update({'rpn_decode_kernel', 'rpn_order_kernel', 'rpn_gather_kernel'})
+            if 'oadg_rpn_topk' in ran:
+                self.kernels.update({'sel_score_kernel', 'sel_refine_kernel<1>', 'sel_refine_kernel<2>', 'sel_count_kernel2',
+                                     'sel_scatter_kernel', 'sel_sort_kernel'})
+        self.info['proposals'] = 'fused' if fused else 'tensor path'
+        ok = len(out) == len(ref) and all(a.shape == b.shape and torch.equal(a, b) for a, b in zip(out, ref))
+        self.exact('rpn proposals (fused vs tensor path)', (len(out),) + tuple(out[0].shape), ok, launched=False)
+        self.info['proposals_per_img'] = [int(a.shape[0]) for a in out]
+
+
+class Auditor(ProposalAudit, HA.Auditor):
+    """rows / failures / kernels / borderline as tests/head_audit.py's Auditor"""
+
+    def __init__(self):
+        super().__init__()
+        self.quiet = 0               # >0 while a reference path runs (its NMS launches are not the product's)
+        self.post = []               # per forward: the captured (rois, cls_score, bbox_pred, metas) of the RoI head
+        self.results = []            # per forward: what the detector returned
+
+    def install(self, mp, det):
+        self.install_proposals(mp)
+        A = self
+        sync = torch.cuda.synchronize
 
         # the RoI head's linears (autocast's casts, the library GEMM) and the RPN's library convolutions
         lin = F.linear
@@ -335,32 +384,7 @@ class Auditor(HA.Auditor):
         mp.setattr(type(rh), 'aug_test_bboxes', aug_test_bboxes)
         return self
 
-    # -- per-launch checks
-    def _check_nms(self, boxes, counts, iou_thr, max_keep, keep, cnt):
-        n_img, M = boxes.shape[:2]
-        mk = max_keep if 0 < max_keep <= M else M
-        words = (M + 63) // 64
-        self.kernels.add('nms_mask_kernel')
-        name = 'nms_scan_kernel<3, 2>' if words <= 64 * 3 else 'nms_scan_kernel<MAX_WORDS_PER_LANE, 1>'
-        c = counts.cpu().tolist()
-        k = cnt.cpu().tolist()
-        for i in range(n_img):
-            ref = nms_expect(boxes[i].float(), int(c[i]), float(iou_thr), mk)
-            got = keep[i, :int(k[i])].cpu().numpy().astype(np.int64)
-            self.exact(name, (n_img, M, int(c[i])), int(k[i]) == len(ref) and np.array_equal(got, ref), check='keep list')
-
-    def _check_proposals(self, ran, out, ref):
-        fused = 'oadg_rpn_gather' in ran
-        if fused:
-            self.kernels.update({'rpn_decode_kernel', 'rpn_order_kernel', 'rpn_gather_kernel'})
-            if 'oadg_rpn_topk' in ran:
-                self.kernels.update({'sel_score_kernel', 'sel_refine_kernel<1>', 'sel_refine_kernel<2>', 'sel_count_kernel2',
-                                     'sel_scatter_kernel', 'sel_sort_kernel'})
-        self.info['proposals'] = 'fused' if fused else 'tensor path'
-        ok = len(out) == len(ref) and all(a.shape == b.shape and torch.equal(a, b) for a, b in zip(out, ref))
-        self.exact('rpn proposals (fused vs tensor path)', (len(out),) + tuple(out[0].shape), ok, launched=False)
-        self.info['proposals_per_img'] = [int(a.shape[0]) for a in out]
-
+    # -- per-forward check
     def check_results(self, det, fwd, results):
         """the post-processing of forward ``fwd`` (its entry of ``self.post``) against the detector's ``results``"""
         kind, props, cls_score, bbox_pred, metas, rescale, cfg = self.post[fwd]
