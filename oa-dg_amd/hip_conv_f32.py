@@ -58,6 +58,19 @@ def _conv(x4, w_krsc, bias, stride, pad, dil, transposed=False, out_hw=(0, 0)):
     return y
 
 
+def _wgrad(x4, g4, R, S, stride, pad, dil):
+    """dW [K4][R][S][C4] fp32 of the padded NHWC operands: split partials, then their sum in split order"""
+    L = _lib.lib()
+    N, C4, H, W = x4.shape
+    K4, Ho, Wo = g4.shape[1], g4.shape[2], g4.shape[3]
+    splits = L.oadg_conv2d_wgrad_f32_splits(N, Ho, Wo, C4, K4, R, S)
+    ws = torch.empty(splits * K4 * R * S * C4, dtype=torch.float32, device=x4.device)
+    dw = torch.empty((K4, R, S, C4), dtype=torch.float32, device=x4.device)
+    check(L.oadg_conv2d_wgrad_f32(ptr(x4), ptr(g4), ptr(dw), ptr(ws), ws.numel() * 4, N, H, W, C4, K4, R, S, stride, pad,
+                                  dil, stream_ptr()), 'oadg_conv2d_wgrad_f32')
+    return dw
+
+
 class _Conv2dF32(torch.autograd.Function):
 
     @staticmethod
@@ -85,14 +98,7 @@ class _Conv2dF32(torch.autograd.Function):
             if gx.shape[1] != C:
                 gx = gx[:, :C]
         if ctx.needs_input_grad[1]:
-            L = _lib.lib()
-            N, C4, H, W = x4.shape
-            K4, Ho, Wo = g4.shape[1], g4.shape[2], g4.shape[3]
-            splits = L.oadg_conv2d_wgrad_f32_splits(N, Ho, Wo, C4, K4, R, S)
-            ws = torch.empty(splits * K4 * R * S * C4, dtype=torch.float32, device=x4.device)
-            dw = torch.empty((K4, R, S, C4), dtype=torch.float32, device=x4.device)
-            check(L.oadg_conv2d_wgrad_f32(ptr(x4), ptr(g4), ptr(dw), ptr(ws), ws.numel() * 4, N, H, W, C4, K4, R, S, stride, pad,
-                                          dil, stream_ptr()), 'oadg_conv2d_wgrad_f32')
+            dw = _wgrad(x4, g4, R, S, stride, pad, dil)
             gw = dw[:K, :, :, :C].permute(0, 3, 1, 2)
         if has_bias and ctx.needs_input_grad[2]:
             gb = gy.sum((0, 2, 3))

@@ -12,29 +12,32 @@ DC5_CFG = os.path.join(ROOT, 'configs', 'oadg', 'faster_rcnn_r101_dc5_1x_dwd_oad
 
 
 def audited_step(dev, monkeypatch, cfg_path, batch, H, W, boxes, classes, box_size, install, on_begin=None,
-                 on_end_backward=None, before_step1=None, speculative_sampling=None):
+                 on_end_backward=None, before_step1=None, speculative_sampling=None, amp_dtype=torch.bfloat16):
     """(out of the audited step, det, wall seconds).  ``install(monkeypatch, det)`` wraps the entry points after step 1;
     ``on_begin()`` / ``on_end_backward(det)`` run inside hip_conv.begin_step / end_backward of the audited step;
     ``before_step1(monkeypatch, det)`` may wrap something for step 1 as well (it stays installed for step 2);
-    ``speculative_sampling`` (not None) sets TrainEngine.speculative_sampling - False: the RoI sampler draws on the host."""
+    ``speculative_sampling`` (not None) sets TrainEngine.speculative_sampling - False: the RoI sampler draws on the host;
+    ``amp_dtype`` None: the fp32 parity step of ``bench.py --dtype fp32`` (no hip_conv.enable(), fp32 pipeline, and
+    begin_step(defer=False): the deferred path is bf16's)."""
     from oadg_amd import Config, build_detector, hip_conv
     from oadg_amd.apis import TrainEngine, build_optimizer, set_random_seed
     from oadg_amd.pipelines import DevicePipeline, SyntheticCityscapes
     cfg = Config.fromfile(cfg_path)
-    hip_conv.enable()
+    if amp_dtype is not None:
+        hip_conv.enable()
     try:
         set_random_seed(0)                       # bench.py main(): the same construction
         det = build_detector(cfg.model)
         det.init_weights(allow_missing_pretrained=True)
         det = det.to(dev).to(memory_format=torch.channels_last).train()
         det.log_vars_on_host = False
-        engine = TrainEngine(det, build_optimizer(det, cfg.optimizer), amp_dtype=torch.bfloat16)
+        engine = TrainEngine(det, build_optimizer(det, cfg.optimizer), amp_dtype=amp_dtype)
         if speculative_sampling is not None:
             engine.speculative_sampling = speculative_sampling
         set_random_seed(1)
         ds = SyntheticCityscapes(img_shape=(H, W), num_boxes=boxes, num_classes=classes, box_size=box_size, seed=0,
                                  device=dev)
-        pipe = DevicePipeline(cfg.data.train.pipeline, dtype=torch.bfloat16)
+        pipe = DevicePipeline(cfg.data.train.pipeline, dtype=amp_dtype or torch.float32)
         if before_step1 is not None:
             before_step1(monkeypatch, det)
         engine.step(pipe(*ds.batch(range(batch))))          # step 1: its optimizer step refreshes the prepared-weight bank
@@ -45,7 +48,10 @@ def audited_step(dev, monkeypatch, cfg_path, batch, H, W, boxes, classes, box_si
         begin, end = hip_conv.begin_step, hip_conv.end_backward
 
         def begin_step(defer):
-            assert defer, 'the audited step must take the deferred path of TrainEngine._step'
+            if amp_dtype is torch.bfloat16:
+                assert defer, 'the audited step must take the deferred path of TrainEngine._step'
+            else:
+                assert not defer, 'an fp32 step defers nothing'
             if on_begin is not None:
                 on_begin()
             return begin(defer)

@@ -873,7 +873,9 @@ class Auditor:
         def linear_bias_grad(x, w, b, relu=False):
             A.hit('linear_bias_grad')
             y = lb(x, w, b, relu)
-            if y.requires_grad:
+            if y.requires_grad and not (A.lin_src.get(w.data_ptr()) is None and x.dtype == torch.float32):
+                # (an fp32 step casts and permutes nothing: its linears are the library's on the parameters themselves, no
+                #  launch of this project's - nothing to map a gradient back through)
                 # the operands of this linear's weight / bias gradient: x, and bf16(dy) * (y > 0) - observed by a hook
                 # on y, which returns nothing (the gradient flows on unchanged)
                 src_w, src_b = A.lin_src.get(w.data_ptr()), A.lin_src.get(b.data_ptr()) if b is not None else None

@@ -19,6 +19,7 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden'))
 import conv_audit as CA  # noqa: E402
+import f32_audit as FA  # noqa: E402
 import head_audit as HA  # noqa: E402
 import infer_audit as IA  # noqa: E402
 import target_audit as TA  # noqa: E402
@@ -323,10 +324,11 @@ LAUNCHES_NOTHING = {
     'oadg_relu_bias_bwd_workspace_bytes', 'oadg_roi_sample_max_rows', 'oadg_rpn_loss_workspace_bytes',
     'oadg_rpn_topk_workspace_bytes', 'oadg_sample_select_workspace_bytes', 'oadg_sgd_blocks', 'oadg_supcon_workspace_bytes',
 }
-# the data pipeline, OA-Mix, the decoders, the corruptions and the fp32 parity convolutions: they run before an audited
-# step installs anything (or not in it at all) and have byte-exact / parity suites of their own (tests/test_hip_oamix.py,
-# test_oracle_oamix.py, test_oamix_buffers.py, test_geometric.py, test_jpeg_decode.py, test_sdgod_dataset.py,
-# test_hip_corrupt.py, test_corrupt.py, test_hip_conv_f32.py) - not part of the audited step
+# the data pipeline, OA-Mix, the decoders and the corruptions: they run before an audited step installs anything (or not
+# in it at all) and have byte-exact suites of their own (tests/test_hip_oamix.py, test_oracle_oamix.py,
+# test_oamix_buffers.py, test_geometric.py, test_jpeg_decode.py, test_sdgod_dataset.py, test_hip_corrupt.py,
+# test_corrupt.py) - not part of the audited step.  (The fp32 parity convolutions are audited launch by launch in the fp32
+# step: tests/f32_audit.py)
 OWN_SUITES = {
     'oadg_chamfer_l2_5x5', 'oadg_glass_shuffle_u8', 'oadg_corrupt_correlate1d', 'oadg_corrupt_defocus', 'oadg_corrupt_elastic',
     'oadg_corrupt_epilogue', 'oadg_corrupt_hsv', 'oadg_corrupt_motion_blur_f64', 'oadg_corrupt_motion_blur_u8',
@@ -335,10 +337,10 @@ OWN_SUITES = {
     'oadg_oamix_bbox_chain_multi', 'oadg_oamix_bbox_levels', 'oadg_oamix_bbox_plan', 'oadg_oamix_bbox_step',
     'oadg_oamix_box_profiles', 'oadg_oamix_compose', 'oadg_oamix_fg_union', 'oadg_oamix_fg_union_rects', 'oadg_oamix_final',
     'oadg_oamix_final_tiles', 'oadg_oamix_gray_sum', 'oadg_oamix_hist', 'oadg_oamix_luts', 'oadg_oamix_normalize',
-    'oadg_oamix_saliency', 'oadg_oamix_saliency_batch', 'oadg_conv2d_f32', 'oadg_conv2d_wgrad_f32',
+    'oadg_oamix_saliency', 'oadg_oamix_saliency_batch',
 }
 CLAIM_SETS = {'conv audit': CA.CLAIMS, 'head audit': HA.CLAIMS, 'infer audit': IA.CLAIMS, 'target audit': TA.CLAIMS,
-              'launches nothing': LAUNCHES_NOTHING, 'own suites': OWN_SUITES}
+              'f32 audit': FA.CLAIMS, 'launches nothing': LAUNCHES_NOTHING, 'own suites': OWN_SUITES}
 # the ``what`` a call reports through _lib.check where it is not the symbol's name
 LABEL_OF = {'oadg_conv2d_nhwc_bf16_ex': 'oadg_conv2d_nhwc_bf16'}
 
