@@ -200,7 +200,6 @@ class FusedSGD(torch.optim.SGD):
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
         self._tables = {}
-        self._slot = 0
 
     def _eligible(self, group):
         if group['momentum'] <= 0 or group['dampening'] != 0 or group['nesterov'] or group.get('maximize', False):
@@ -238,7 +237,7 @@ class FusedSGD(torch.optim.SGD):
         lists = [self._eligible(g) for g in self.param_groups] if (self.FUSED and closure is None) else [None]
         if any(l is None for l in lists):
             return super().step(closure)
-        from . import _lib
+        from . import _lib, staging
         L = _lib.lib()
         for gi, (group, ps) in enumerate(zip(self.param_groups, lists)):
             if not ps:
@@ -251,11 +250,7 @@ class FusedSGD(torch.optim.SGD):
                 for i, p in enumerate(ps):
                     tab[i]['numel'], tab[i]['first_block'] = p.numel(), blocks
                     blocks += int(L.oadg_sgd_blocks(p.numel()))
-                dev = ps[0].device
-                ent = self._tables[gi] = dict(
-                    key=key, tab=tab, blocks=blocks,
-                    pinned=[torch.empty(tab.nbytes, dtype=torch.uint8).pin_memory() for _ in range(2)],
-                    events=[None, None], dev=torch.empty(tab.nbytes, dtype=torch.uint8, device=dev))
+                ent = self._tables[gi] = dict(key=key, tab=tab, blocks=blocks)
             tab = ent['tab']
             bufs, first = [], []
             for p in ps:
@@ -269,15 +264,8 @@ class FusedSGD(torch.optim.SGD):
             tab['grad'] = [p.grad.data_ptr() for p in ps]
             tab['momentum'] = [b.data_ptr() for b in bufs]
             tab['first_step'] = first
-            self._slot ^= 1
-            pin = ent['pinned'][self._slot]
-            if ent['events'][self._slot] is not None:
-                ent['events'][self._slot].synchronize()        # the copy out of this staging slot two steps ago is done
-            pin.numpy()[:] = tab.view(np.uint8)
-            ent['dev'].copy_(pin, non_blocking=True)
-            ev = ent['events'][self._slot] = ent['events'][self._slot] or torch.cuda.Event()
-            ev.record()
-            _lib.check(L.oadg_sgd_step_multi(_lib.ptr(ent['dev']), len(ps), ent['blocks'], float(group['lr']),
+            tdev = staging.upload(tab, ps[0].device)
+            _lib.check(L.oadg_sgd_step_multi(_lib.ptr(tdev), len(ps), ent['blocks'], float(group['lr']),
                                              float(group['momentum']), float(group['weight_decay']), _lib.stream_ptr()),
                        'oadg_sgd_step_multi')
             # the kernel wrote the parameters behind ATen's back: bump their version counters, as the in-place ops of
@@ -641,9 +629,8 @@ class TrainEngine:
         for r in recs:
             if r['gen'] is not None:
                 r['gen'].sync_host()     # (also brings torch's CPU generator up to date with the device's draws)
-            else:
-                r['event'].synchronize()  # (a call this rank drew on the host: only the shared flags travel)
-            short = short or bool(r['meta'][2 * r['B']:].any())
+            # (a call this rank drew on the host has no generator: only the shared flags travel)
+            short = short or bool(r['copy'].wait()[2 * r['B']:].any())
         if short:
             self.respeculated += 1
             torch.set_rng_state(saved[0])

@@ -9,6 +9,7 @@ import os
 import numpy as np
 import torch
 
+from .. import staging
 from ..registry import BBOX_ASSIGNERS, BBOX_CODERS, BBOX_SAMPLERS, IOU_CALCULATORS
 
 
@@ -192,7 +193,7 @@ class MaxIoUAssigner:
         if valids is not None and any(v is not None for v in valids):
             vd = torch.stack([v if v is not None else torch.ones(N, dtype=torch.bool, device=dev)
                               for v in valids]).to(torch.uint8).contiguous()
-        gcnt = _pinned_to(torch.tensor(counts_host, dtype=torch.int32), dev)
+        gcnt = staging.upload(np.asarray(counts_host, dtype=np.int32), dev)
         gt_inds = torch.empty((B, N), dtype=torch.long, device=dev)
         max_ov = torch.empty((B, N), dtype=torch.float32, device=dev)
         labels = torch.empty((B, N), dtype=torch.long, device=dev) if (with_labels and Gmax) else None
@@ -406,13 +407,6 @@ class RandomSampler:
         return SamplingResult(pos_inds, neg_inds, bboxes, gt_bboxes, assign_result, gt_flags)
 
 
-def _pinned_to(t_cpu, device):
-    """async H2D of a small host tensor (pinned staging; never blocks the host on the stream)."""
-    if device.type != 'cuda':
-        return t_cpu.to(device)
-    return t_cpu.pin_memory().to(device, non_blocking=True)
-
-
 _JOB_DTYPE = np.dtype([('gt_inds', np.uint64), ('n', np.int64), ('mode', np.int32), ('k', np.int32),
                        ('all', np.int32), ('rank_off', np.int32), ('out_off', np.int64)])      # oadg_select_job
 
@@ -432,22 +426,16 @@ class PendingSampling:
         self.sampler, self.prepared, self.gt_bboxes_list = sampler, prepared, gt_bboxes_list
         self.added_pos = added_pos
         self.results = None
-        self.event = None
-        if counts_dev is None:
-            self.counts = []
-        elif counts_dev.is_cuda:
-            self.counts = torch.empty(counts_dev.shape, dtype=counts_dev.dtype, pin_memory=True)
-            self.counts.copy_(counts_dev, non_blocking=True)
-            self.event = torch.cuda.Event()
-            self.event.record()
-        else:
-            self.counts = counts_dev
+        # (``counts`` / ``event``: the read-back's pinned destination and the event behind it, for whoever inspects them)
+        self.copy = None if counts_dev is None else staging.readback(counts_dev)
+        self.counts = [] if self.copy is None else self.copy.host
+        self.event = None if self.copy is None else self.copy.event
 
     def _plan(self):
         """Host side of the draw, image by image in the reference's order (positives, then negatives):
         [(k_pos, ranks_pos | None, k_neg, ranks_neg | None)]; ``None`` = every candidate."""
         sampler = self.sampler
-        counts = self.counts.tolist() if isinstance(self.counts, torch.Tensor) else self.counts
+        counts = [] if self.copy is None else self.copy.wait().tolist()      # (waits for THAT copy only)
         if self.added_pos is not None:
             counts = [(c[0] + a, c[1]) for c, a in zip(counts, self.added_pos)]
         num_pos_exp = int(sampler.num * sampler.pos_fraction)
@@ -486,7 +474,7 @@ class PendingSampling:
             max_n = max(max_n, gi.numel())
         rk = np.concatenate(ranks) if ranks else np.zeros(1, np.int32)
         blob = np.concatenate([jobs.view(np.uint8), rk.view(np.uint8)])
-        blob_dev = _pinned_to(torch.from_numpy(blob), dev)
+        blob_dev = staging.upload(blob, dev)
         jobs_dev = blob_dev[:jobs.nbytes]
         ranks_dev = blob_dev[jobs.nbytes:]
         sel = torch.empty(max(out_off, 1), dtype=torch.long, device=dev)
@@ -525,11 +513,8 @@ class PendingSampling:
                     meta = torch.zeros(3 * B, dtype=torch.int32, device=dev)
                     meta[2 * B:] = 2
                     dist.all_reduce(meta[2 * B:], op=dist.ReduceOp.MAX, group=_SPEC_GROUP[0])
-                    host = torch.empty(3 * B, dtype=torch.int32).pin_memory()
-                    host.copy_(meta, non_blocking=True)
-                    ev = torch.cuda.Event()
-                    ev.record()
-                    _SPEC.append(dict(meta=host, B=B, gen=None, event=ev))
+                    copy = staging.readback(meta)
+                    _SPEC.append(dict(meta=copy.host, B=B, gen=None, copy=copy))
                 return None
             images[i].gt_inds, images[i].n = gi.data_ptr(), gi.numel()
         num = int(sampler.num)
@@ -546,10 +531,9 @@ class PendingSampling:
         if _SPEC_GROUP is not None:
             # every rank must take the same decision about repeating the step (its collectives): share the flags
             dist.all_reduce(flags, op=dist.ReduceOp.MAX, group=_SPEC_GROUP[0])
-        host = torch.empty(3 * B, dtype=torch.int32).pin_memory()
-        host.copy_(meta, non_blocking=True)
-        gen.download_async()                      # (its event also covers the copy above: same stream)
-        _SPEC.append(dict(meta=host, B=B, gen=gen))
+        copy = staging.readback(meta)
+        gen.download_async()
+        _SPEC.append(dict(meta=copy.host, B=B, gen=gen, copy=copy))
         self.results = [DeviceSamplingResult(sel[i], counts[i], num, prep[1], self.gt_bboxes_list[i], prep[0], prep[2])
                         for i, prep in enumerate(self.prepared)]
         return self.results
@@ -561,8 +545,6 @@ class PendingSampling:
             res = self._finish_device()
             if res is not None:
                 return res
-        if self.event is not None:
-            self.event.synchronize()
         plan = self._plan()
         dev = self.prepared[0][1].device if self.prepared else None
         if dev is not None and dev.type == 'cuda':
@@ -797,7 +779,7 @@ def bbox2roi(bbox_list):
         # one index column for the whole batch (built on the host from the known sizes, uploaded through pinned memory)
         # and two concatenations, instead of a fill + a concatenation per image
         first = bbox_list[0]
-        idx = _pinned_to(torch.from_numpy(np.repeat(np.arange(len(sizes), dtype=np.float32), sizes)), first.device)
+        idx = staging.upload(np.repeat(np.arange(len(sizes), dtype=np.float32), sizes), first.device)
         boxes = torch.cat([b[:, :4] for b in bbox_list], 0)
         return torch.cat([idx.to(boxes.dtype)[:, None], boxes], dim=1)
     rois = []

@@ -22,6 +22,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
+from . import staging
 from .registry import DATASETS, build_from_cfg
 
 
@@ -93,8 +94,7 @@ class CocoDataset:
             want = max(4, len(self._decode_cores))
         self.decode_workers = want
         self.ring_slots = 6            # pinned batch buffers per (batch, shape): more than tools/train.py keeps in flight
-        self._rings, self._ring_lock = {}, threading.Lock()
-        self._coef_rings = {}          # pinned JPEG coefficient buffers, keyed by capacity (a power of two)
+        self._rings, self._ring_lock = {}, threading.Lock()     # staging.Ring per batch shape / per coefficient capacity
         self.jpeg_decodes = dict(native=0, pil=0)       # JPEG files decoded by csrc/jpeg_decode.hip / by PIL
         self._count_lock = threading.Lock()
         self._pool = ThreadPoolExecutor(want, thread_name_prefix='oadg-decode', initializer=self._place_worker)
@@ -217,33 +217,23 @@ class CocoDataset:
             self.jpeg_decodes[path] += k
 
     def _slot(self, n, H, W):
-        """a pinned [n,H,W,3] batch buffer from a small ring (allocated once per shape: pinning 25 MB per batch costs more
-        than decoding it); a slot is reused only after the upload that read it has finished"""
-        return self._ring_slot(self._rings, (n, H, W), lambda: torch.empty((n, H, W, 3), dtype=torch.uint8))
+        """a reserved slot holding a pinned [n,H,W,3] batch, from a small ring per shape (allocated once per shape: pinning
+        25 MB per batch costs more than decoding it); a slot is reused only after the upload that read it has finished"""
+        return self._reserve((n, H, W), n * H * W * 3)
 
     def _coef_slot(self, nbytes):
-        """a pinned uint8 buffer of at least ``nbytes`` for the JPEG coefficients + descriptors of a batch, from a ring
-        keyed by capacity (the next power of two, at least 1 MiB): a handful of rings whatever the image shapes"""
+        """a reserved slot of at least ``nbytes`` for the JPEG coefficients + descriptors of a batch, from a ring keyed by
+        capacity (the next power of two, at least 1 MiB): a handful of rings whatever the image shapes"""
         cap = 1 << max(20, (int(nbytes) - 1).bit_length())
-        return self._ring_slot(self._coef_rings, cap, lambda: torch.empty(cap, dtype=torch.uint8))
+        return self._reserve(cap, cap)
 
-    def _ring_slot(self, rings, key, alloc):
+    def _reserve(self, key, nbytes):
         with self._ring_lock:
-            ring = rings.setdefault(key, dict(bufs=[], events=[], next=0))
-            if len(ring['bufs']) < self.ring_slots:
-                buf = alloc()
-                if torch.device(self.device).type == 'cuda':
-                    buf = buf.pin_memory()
-                ring['bufs'].append(buf)
-                ring['events'].append(None)
-                k = len(ring['bufs']) - 1
-            else:
-                k = ring['next']
-                ring['next'] = (k + 1) % self.ring_slots
-            ev = ring['events'][k]
-        if ev is not None:
-            ev.synchronize()
-        return ring, k
+            ring = self._rings.get(key)
+            if ring is None:
+                ring = self._rings[key] = staging.Ring(self.ring_slots, nbytes)
+            ring.slots = self.ring_slots        # (tools/train.py raises it: holds for the slots not created yet)
+        return ring.reserve(nbytes)
 
     def batch(self, indices):
         """(uint8 [N,H,W,3] on the device, list of float32 [n,4] boxes, list of int64 labels)."""
@@ -256,17 +246,15 @@ class CocoDataset:
             dev = self._batch_jpeg(indices, H, W)
             anns = [self.get_ann_info(i) for i in indices]
             return dev, [a['bboxes'] for a in anns], [a['labels'] for a in anns]
-        ring, k = self._slot(len(indices), H, W)
-        host = ring['bufs'][k]
-        views = host.numpy()
-        list(self._pool.map(lambda a: self.decode_into(a[1], views[a[0]]), enumerate(indices)))
-        if torch.device(self.device).type == 'cuda':
-            dev = host.to(self.device, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            ring['events'][k] = ev
-        else:
-            dev = host.clone()
+        n = len(indices)
+        slot = self._slot(n, H, W)
+        views = slot.host[:n * H * W * 3].view(n, H, W, 3).numpy()
+        try:
+            list(self._pool.map(lambda a: self.decode_into(a[1], views[a[0]]), enumerate(indices)))
+        except BaseException:
+            slot.release()
+            raise
+        dev = slot.commit(n * H * W * 3, self.device).view(n, H, W, 3)
         anns = [self.get_ann_info(i) for i in indices]
         return dev, [a['bboxes'] for a in anns], [a['labels'] for a in anns]
 
@@ -281,9 +269,8 @@ class CocoDataset:
         slot = int(L.oadg_jpeg_coef_capacity(H, W))
         dbytes = n * D                                   # (a multiple of 16: the coefficients stay 16-byte aligned)
         need = dbytes + 2 * n * slot
-        ring, k = self._coef_slot(need)
-        host = ring['bufs'][k]
-        arr = host.numpy()
+        cslot = self._coef_slot(need)
+        arr = cslot.host.numpy()
         base = arr.ctypes.data
 
         def work(a):
@@ -297,16 +284,19 @@ class CocoDataset:
             img = np.empty((H, W, 3), dtype=np.uint8)
             self.decode_into(idx, img)
             return img
-        host_imgs = list(self._pool.map(work, enumerate(indices)))
+        try:
+            host_imgs = list(self._pool.map(work, enumerate(indices)))
+        except BaseException:
+            cslot.release()
+            raise
         native = sum(a is None for a in host_imgs)
         self._count('native', native)
         out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=self.device)
         if native:
-            dev = host[:need].to(self.device, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            ring['events'][k] = ev
+            dev = cslot.commit(need, self.device)
             hip_ops.jpeg_pixels_bgr(dev[dbytes:].view(torch.int16), dev[:dbytes], out, slot)
+        else:
+            cslot.release()
         for i, img in enumerate(host_imgs):
             if img is not None:
                 out[i].copy_(torch.from_numpy(img))

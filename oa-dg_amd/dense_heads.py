@@ -12,7 +12,7 @@ from torch.profiler import record_function as _rf
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import hip_ops
+from . import hip_ops, staging
 from .core import anchor_inside_flags, images_to_levels, multi_apply, unmap
 from .core.bbox import sample_many, sample_many_begin
 from .layers import Conv2d, conv2d, normal_init
@@ -503,7 +503,7 @@ class RPNHead(AnchorHead):
         CPU tensors) - the tensor path runs."""
         import ctypes
         from . import _lib
-        from .core.bbox import DeltaXYWHBBoxCoder, _pinned_to
+        from .core.bbox import DeltaXYWHBBoxCoder
         coder = self.bbox_coder
         dev = cls_scores[0].device
         if not (self.FUSED_PROPOSALS and dev.type == 'cuda' and self.use_sigmoid_cls and type(coder) is DeltaXYWHBBoxCoder
@@ -564,7 +564,7 @@ class RPNHead(AnchorHead):
             return None
         clip = bool(getattr(coder, 'clip_border', True))
         lim_host = torch.tensor([[m['img_shape'][1], m['img_shape'][0]] for m in img_metas[:n_img]], dtype=torch.float32)
-        lim = _pinned_to(lim_host, dev)
+        lim = staging.upload(lim_host, dev)
         means = (ctypes.c_float * 4)(*[float(v) for v in coder.means])
         stds = (ctypes.c_float * 4)(*[float(v) for v in coder.stds])
         max_ratio = float(np.float32(np.abs(np.log(16 / 1000))))
@@ -657,8 +657,8 @@ class RPNHead(AnchorHead):
             props = self.bbox_coder.decode(anchors.reshape(-1, 4), deltas.reshape(-1, 4),
                                            max_shape=None).view(n_img, M, 4)
             if getattr(self.bbox_coder, 'clip_border', True):
-                lim = torch.tensor([[m['img_shape'][1], m['img_shape'][0]] for m in img_metas[:n_img]],
-                                   dtype=props.dtype).pin_memory().to(device, non_blocking=True)      # [I, (W, H)]
+                lim = staging.upload(torch.tensor([[m['img_shape'][1], m['img_shape'][0]] for m in img_metas[:n_img]],
+                                                  dtype=torch.float32), device).to(props.dtype)    # [I, (W, H)]
                 lim = lim.repeat(1, 2)[:, None, :]                                                   # x1 y1 x2 y2 limits
                 props = torch.minimum(props.clamp(min=0), lim)
         valid = torch.ones_like(scores, dtype=torch.bool)

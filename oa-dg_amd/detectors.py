@@ -8,8 +8,8 @@ import torch.distributed as dist
 import torch.nn as nn
 from torch.profiler import record_function as _rf
 
+from . import staging
 from .core import bbox_overlaps_np
-from .core.bbox import _pinned_to
 from .registry import DETECTORS, build_backbone, build_head, build_neck
 
 
@@ -235,16 +235,11 @@ class BaseDetector(nn.Module):
         pinned buffer asynchronously and the PREVIOUS step's copy (long complete) is the one asserted on."""
         prev = getattr(self, '_log_count_pending', None)
         if prev is not None:
-            buf, ev, exp, nm = prev
-            ev.synchronize()
-            assert int(round(buf.item())) == exp, \
+            copy, exp, nm = prev
+            assert int(round(copy.wait().item())) == exp, \
                 f'loss log variables are different across GPUs! rank {dist.get_rank()} keys: {nm}'
         if count.is_cuda:
-            buf = torch.empty((), dtype=count.dtype, pin_memory=True)
-            buf.copy_(count, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            self._log_count_pending = (buf, ev, expect, names)
+            self._log_count_pending = (staging.readback(count), expect, names)
         else:
             assert int(round(count.item())) == expect, \
                 f'loss log variables are different across GPUs! rank {dist.get_rank()} keys: {names}'
@@ -387,7 +382,7 @@ class TwoStageDetector(BaseDetector):
                                             bboxes_xy=gts[i % kwargs['num_views']], scales=cfg['scales'],
                                             ratios=cfg['ratios'], iou_max=cfg['iou_max'], iou_min=cfg['iou_min'])
             out[i] = np.concatenate([out[i], new[:, :4].astype(np.float32)], axis=0)
-        return [_pinned_to(torch.from_numpy(np.ascontiguousarray(o, dtype=np.float32)), device) for o in out]
+        return [staging.upload(np.ascontiguousarray(o, dtype=np.float32), device) for o in out]
 
 
 @DETECTORS.register_module()

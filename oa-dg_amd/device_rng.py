@@ -7,6 +7,7 @@ Now the engine state (624 words + ``left`` + ``next``) travels instead: uploaded
 asynchronous 2.5 KB copy), advanced by the kernel exactly as ATen would, copied back behind it; the host generator is
 set to the advanced state when the trainer next needs it (``sync_host``, at the end of the step - by then the event has
 long fired).  Seeded runs stay draw-for-draw equal to the reference.
+The two pinned state buffers are its own, not slots of staging.py: one state in flight, asserted, is no ring.
 """
 import numpy as np
 import torch

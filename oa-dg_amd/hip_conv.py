@@ -10,7 +10,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, staging
 from ._lib import check, ptr, stream_ptr
 
 _ZEROS = {}
@@ -145,7 +145,6 @@ def _close_shared_leftovers():
 _CS_JOB = np.dtype([('part', np.uint64), ('out', np.uint64), ('dgamma', np.uint64), ('mean', np.uint64),
                     ('var', np.uint64), ('rows', np.int32), ('K', np.int32), ('first_block', np.int32),
                     ('eps', np.float32)])                                                           # oadg_colsum_job
-_CS_STAGE = {}
 
 
 class _PendingColsum:
@@ -204,19 +203,7 @@ def flush_colsums():
             dg, mean, var, eps = e.fix
             r['dgamma'], r['mean'], r['var'], r['eps'] = dg.data_ptr(), mean.data_ptr(), var.data_ptr(), eps
         blocks += (K + 15) // 16
-    st = _CS_STAGE.get(dev)
-    if st is None or st[0][0].numel() < tab.nbytes:
-        n = max(tab.nbytes, 256 * _CS_JOB.itemsize)
-        st = _CS_STAGE[dev] = ([torch.empty(n, dtype=torch.uint8).pin_memory() for _ in range(4)],
-                               [torch.empty(n, dtype=torch.uint8, device=dev) for _ in range(4)], [0], [None] * 4)
-    k = st[2][0] = (st[2][0] + 1) % 4      # a few flushes per step at most (one per gradient bucket): four slots
-    pin, tdev = st[0][k], st[1][k]
-    if st[3][k] is not None:
-        st[3][k].synchronize()             # the copy out of this staging slot four flushes ago is done
-    pin.numpy()[:tab.nbytes] = tab.view(np.uint8)
-    tdev[:tab.nbytes].copy_(pin[:tab.nbytes], non_blocking=True)
-    st[3][k] = st[3][k] or torch.cuda.Event()
-    st[3][k].record()
+    tdev = _STAGE.upload(tab, dev)         # a few flushes per step at most (one per gradient bucket)
     check(_lib.lib().oadg_colsum_reduce_multi(ptr(tdev), len(pend), blocks, stream_ptr()), 'oadg_colsum_reduce_multi')
     for e in pend:
         for prm, alias in e.targets:
@@ -255,41 +242,9 @@ _PB_JOB = np.dtype([('part', 'u8'), ('gbias', 'u8'), ('w', 'u8'), ('scale', 'u8'
 assert _WG_JOB.itemsize == 104 and _PB_JOB.itemsize == 96
 
 
-class _TableStage:
-    """host table -> device memory without a blocking copy: a ring of pinned + device buffers per device; a slot is
-    reused only after the copy issued from it ``SLOTS`` uploads ago has completed (event)"""
-    SLOTS = 16
-
-    def __init__(self):
-        self.dev = {}
-
-    def upload(self, tab, device):
-        raw = tab.view(np.uint8).reshape(-1)
-        st = self.dev.get(device)
-        if st is None or st[0][0].numel() < raw.nbytes:
-            n = max(raw.nbytes, 64 * 104)
-            st = self.dev[device] = ([torch.empty(n, dtype=torch.uint8).pin_memory() for _ in range(self.SLOTS)],
-                                     [torch.empty(n, dtype=torch.uint8, device=device) for _ in range(self.SLOTS)], [0],
-                                     [None] * self.SLOTS)
-        k = st[2][0] = (st[2][0] + 1) % len(st[0])
-        if st[3][k] is not None and not st[3][k].query():
-            # the copy issued from this slot one lap ago is still queued (behind the backward kernels of THIS pass): take a
-            # new slot instead of stalling the host's run-ahead on it (ADVICE r4)
-            n = st[0][0].numel()
-            st[0].insert(k, torch.empty(n, dtype=torch.uint8).pin_memory())
-            st[1].insert(k, torch.empty(n, dtype=torch.uint8, device=device))
-            st[3].insert(k, None)
-        pin, tdev = st[0][k], st[1][k]
-        if st[3][k] is not None:
-            st[3][k].synchronize()
-        pin.numpy()[:raw.nbytes] = raw
-        tdev[:raw.nbytes].copy_(pin[:raw.nbytes], non_blocking=True)
-        st[3][k] = st[3][k] or torch.cuda.Event()
-        st[3][k].record()
-        return tdev
-
-
-_TABLES = _TableStage()
+# host table -> device memory without a blocking copy (weight-gradient jobs, BN-fold consumer jobs, column-sum jobs): a slot
+# whose last copy is still queued is stepped around, not waited for
+_STAGE = staging.Ring(16, 64 * _WG_JOB.itemsize, grow_when_busy=True)
 
 
 def wgrad_work(N, Ho, Wo, C, K, R, S):
@@ -360,7 +315,7 @@ def wgrad_multi(jobs, target_blocks=256):
     if name:
         e0 = torch.cuda.Event(enable_timing=True)
         e0.record()
-    tdev = _TABLES.upload(tab, dev)
+    tdev = _STAGE.upload(tab, dev)
     check(L.oadg_conv2d_wgrad_multi(ptr(tdev), len(jobs), int(total), xcd_first, ptr(_zeros(dev)), stream_ptr()),
           'oadg_conv2d_wgrad_multi')
     if name:
@@ -413,7 +368,7 @@ def flush_wgrads():
         r['K'], r['C'], r['R'], r['S'], r['w_krsc'], r['first_block'] = K, C, R, S, flags, first
         first += K
         max_crs = max(max_crs, C * R * S)
-    tdev = _TABLES.upload(tab, dev)
+    tdev = _STAGE.upload(tab, dev)
     check(L.oadg_prep_conv_weights_bwd_parts_multi(ptr(tdev), len(cons), first, max_crs, stream_ptr()),
           'oadg_prep_conv_weights_bwd_parts_multi')
     for j in jobs:

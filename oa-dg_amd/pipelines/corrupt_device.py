@@ -4,16 +4,15 @@
 Only the deterministic filtering and resampling moves.  Every random draw is made here on the host, with the numpy calls,
 shapes and order of ``corrupt()``, image by image in batch order, so numpy's global stream ends where the host loop leaves
 it.  The filter weights and the uint8 -> float tables are computed by the same numpy expressions as the host path, then
-uploaded with the draws through one pinned buffer per batch (a small ring: a slot is refilled only after the upload that
-read it has finished).  glass_blur's sequential shuffle stays the host loop (csrc/corrupt_host.hip) between its two device
-blurs.  Channel order is left as the batch holds it.
+uploaded with the draws through one pinned slot per batch (staging.upload).  glass_blur's sequential shuffle stays the host
+loop (csrc/corrupt_host.hip) between its two device blurs.  Channel order is left as the batch holds it.
 """
 import time
 
 import numpy as np
 import torch
 
-from .. import _lib, hip_ops
+from .. import _lib, hip_ops, staging
 from . import corrupt as C
 
 # seconds spent on the host side of the device path (draws, weights, tap tables, glass_blur's shuffle): tools/bench_corrupt.py
@@ -24,46 +23,8 @@ _LUT32_ZOOM = (np.arange(256) / 255.).astype(np.float32)          # zoom_blur: (
 _LUT32 = np.arange(256, dtype=np.float32) / 255.                  # snow, elastic: np.array(x, dtype=np.float32) / 255.
 
 
-class _Staging:
-    """pinned host memory for the uploads of a batch, a ring of SLOTS buffers (datasets.CocoDataset._ring_slot): a slot
-    is rewritten only after the event recorded behind its last upload has completed"""
-    SLOTS = 2
-
-    def __init__(self):
-        self.bufs, self.events, self.next = [None] * self.SLOTS, [None] * self.SLOTS, 0
-
-    def upload(self, arrays, device):
-        offs, total = [], 0
-        for a in arrays:
-            total = (total + 255) // 256 * 256
-            offs.append(total)
-            total += a.nbytes
-        k = self.next
-        self.next = (k + 1) % self.SLOTS
-        if self.events[k] is not None:
-            self.events[k].synchronize()
-        if self.bufs[k] is None or self.bufs[k].numel() < total:
-            self.bufs[k] = torch.empty(1 << max(20, (total - 1).bit_length()), dtype=torch.uint8).pin_memory()
-        host = self.bufs[k].numpy()
-        for a, o in zip(arrays, offs):
-            host[o:o + a.nbytes] = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
-        dev = self.bufs[k][:total].to(device, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self.events[k] = ev
-        out = []
-        for a, o in zip(arrays, offs):
-            dt = torch.from_numpy(np.empty(0, a.dtype)).dtype
-            out.append(dev[o:o + a.nbytes].view(dt).view(a.shape))
-        return out
-
-
-_STAGING = {}
-
-
 def _upload(device, *arrays):
-    st = _STAGING.setdefault(device, _Staging())
-    return st.upload([np.ascontiguousarray(a) for a in arrays], device)
+    return staging.upload(arrays, device)
 
 
 def gaussian_weights(sigma, truncate):

@@ -13,7 +13,7 @@ import os
 import numpy as np
 import torch
 
-from .. import _lib
+from .. import _lib, staging
 from .._lib import check, ptr, stream_ptr
 from ..registry import DATASETS, PIPELINES, build_from_cfg
 from .corrupt import Corrupt
@@ -298,10 +298,8 @@ class DevicePipeline:
         if geo_meta is not None:
             for m, g in zip(out['img_metas'], geo_meta):
                 m.update({k: v for k, v in g.items() if k != 'img_shape'})
-        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).pin_memory().to(  # noqa: E731
-            dev, non_blocking=True)
-        out['gt_bboxes'] = [up(b, np.float32) for b in gt_bboxes]
-        out['gt_labels'] = [up(l, np.int64) for l in gt_labels]
+        out['gt_bboxes'] = [staging.upload(np.ascontiguousarray(b, dtype=np.float32), dev) for b in gt_bboxes]
+        out['gt_labels'] = [staging.upload(np.ascontiguousarray(l, dtype=np.int64), dev) for l in gt_labels]
         if self.oamix is not None and self.oamix.num_views > 1:
             assert self.oamix.num_views == 2 and self.oamix.keep_orig
             om = self.oamix

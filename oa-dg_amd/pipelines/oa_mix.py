@@ -36,7 +36,7 @@ def use_random_state(rs):
     _TLS.rs = rs
 import torch
 
-from .. import _lib
+from .. import _lib, staging
 from .._lib import (OP_BG_WARP, OP_IMAGE, OP_LUT_AUTOCONTRAST, OP_LUT_EQUALIZE, OP_POSTERIZE, OP_SOLARIZE,
                     OP_WARP_NEG, RegionOp, check, ptr, stream_ptr)
 from ..core.bbox import bbox_overlaps_np
@@ -174,53 +174,7 @@ def geo_matrix(kind, severity, img_size, center=None, size_for_level=None):
     return np.float32([[1, 0, -lvl], [0, 1, 0]]) if ax == 0 else np.float32([[1, 0, 0], [0, 1, -lvl]])
 
 
-class _PinnedRing:
-    """Per-thread ring of pinned staging buffers for the small descriptor uploads: ``tensor.pin_memory()`` allocates
-    (hipHostMalloc, ~2 ms for a 4096-box descriptor table) on every call; a slot of the ring is reused once the copy
-    that read it has completed (event recorded behind the copy on its stream)."""
-    SLOTS = 96
-
-    def __init__(self):
-        self.bufs, self.events, self.k = [None] * self.SLOTS, [None] * self.SLOTS, 0
-
-    def slot(self, nbytes):
-        """(slot number, pinned uint8 buffer of >= nbytes) - the caller fills it, enqueues the copy and records the slot's
-        event behind it"""
-        k, self.k = self.k, (self.k + 1) % self.SLOTS
-        if self.events[k] is not None:
-            self.events[k].synchronize()
-        buf = self.bufs[k]
-        if buf is None or buf.numel() < nbytes:
-            buf = self.bufs[k] = torch.empty((max(4096, 1 << int(max(nbytes, 2) - 1).bit_length()),), dtype=torch.uint8,
-                                             pin_memory=True)
-        return k, buf
-
-    def stage(self, raw):
-        k, self.k = self.k, (self.k + 1) % self.SLOTS
-        if self.events[k] is not None:
-            self.events[k].synchronize()
-        buf = self.bufs[k]
-        if buf is None or buf.numel() < raw.size:
-            buf = self.bufs[k] = torch.empty((max(4096, 1 << int(raw.size - 1).bit_length()),), dtype=torch.uint8,
-                                             pin_memory=True)
-        buf.numpy()[:raw.size] = raw
-        return k, buf[:raw.size]
-
-
-def _upload(arr, device):
-    """small host array -> device tensor (same dtype / shape) without blocking the host on the stream"""
-    arr = np.ascontiguousarray(arr)
-    ring = getattr(_TLS, 'ring', None)
-    if ring is None:
-        ring = _TLS.ring = _PinnedRing()
-    if arr.size == 0:
-        return torch.from_numpy(arr).to(device)
-    k, src = ring.stage(arr.view(np.uint8).reshape(-1))
-    dst = torch.empty((src.numel(),), dtype=torch.uint8, device=device)
-    dst.copy_(src, non_blocking=True)
-    ev = ring.events[k] = ring.events[k] or torch.cuda.Event()
-    ev.record()
-    return dst.view(torch.from_numpy(arr[:0]).dtype).view(arr.shape)
+PLAN_SLOTS = 96        # pinned slots for the plans handed to planner threads (held until execute() commits them)
 
 
 class _ImageState:
@@ -250,7 +204,7 @@ class _ImageState:
             sg = np.zeros((nb, 2), np.float64)
             for st, r in zip(states, rows):
                 qb[r:r + st.n], sg[r:r + st.n] = st._qbox_host, st._sigma_host
-            qbox_dev, sigma_dev = _upload(qb, dev), _upload(sg, dev)
+            qbox_dev, sigma_dev = staging.upload(qb, dev), staging.upload(sg, dev)
             check(L.oadg_oamix_box_profiles(ptr(qbox_dev), ptr(sigma_dev), nb, H, W, spatial_ratio, ptr(My), ptr(Mx),
                                             stream_ptr()), 'oadg_oamix_box_profiles')
         for st, r in zip(states, rows):
@@ -261,19 +215,16 @@ class _ImageState:
         if tot:
             ib = np.concatenate([np.array(st.gt, dtype=np.int32).reshape(-1, 4) for st in states], 0)
             img_of = np.concatenate([np.full((st.n,), i, np.int32) for i, st in enumerate(states)])
-            ib_dev, of_dev = _upload(ib, dev), _upload(img_of, dev)
+            ib_dev, of_dev = staging.upload(ib, dev), staging.upload(img_of, dev)
             scores_dev = torch.empty((tot,), dtype=torch.float64, device=dev)
             nbytes = L.oadg_oamix_saliency_workspace_bytes(tot)
             ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
             check(L.oadg_oamix_saliency_batch(ptr(imgs), int(imgs.stride(0)), ptr(of_dev), H, W, ptr(ib_dev), tot, spatial_ratio,
                                               ptr(scores_dev), ptr(ws), nbytes, stream_ptr()), 'oadg_oamix_saliency_batch')
-            host = torch.empty((tot,), dtype=torch.float64, pin_memory=True)
-            host.copy_(scores_dev, non_blocking=True)
-            evt = torch.cuda.Event()
-            evt.record()
+            copy = staging.readback(scores_dev)
             off = 0
             for st in states:
-                st._scores_host, st._scores_evt = host[off:off + st.n], evt
+                st._scores_copy = (copy, off, off + st.n)
                 st._keep += (ib_dev, of_dev, scores_dev, ws, qbox_dev, sigma_dev)
                 off += st.n
         return states
@@ -285,25 +236,22 @@ class _ImageState:
         self.My = torch.empty((max(n, 1), H), dtype=torch.float32, device=dev)
         self.Mx = torch.empty((max(n, 1), W), dtype=torch.float32, device=dev)
         if n:
-            self._qbox = _upload(self._qbox_host, dev)
-            self._sigma = _upload(self._sigma_host, dev)
+            self._qbox = staging.upload(self._qbox_host, dev)
+            self._sigma = staging.upload(self._sigma_host, dev)
             check(L.oadg_oamix_box_profiles(ptr(self._qbox), ptr(self._sigma), n, H, W, spatial_ratio,
                                             ptr(self.My), ptr(self.Mx), stream_ptr()), 'oadg_oamix_box_profiles')
         self._union()
         # --- saliency scores (oa_mix.py:98-111): launched now, read when object-aware mixing needs them -----
         if n:
             ib = np.array(self.gt, dtype=np.int32)
-            self._ibox = _upload(ib, dev)
+            self._ibox = staging.upload(ib, dev)
             self._scores_dev = torch.empty((n,), dtype=torch.float64, device=dev)
             nb = L.oadg_oamix_saliency_workspace_bytes(n)
             self._sal_ws = torch.empty((nb,), dtype=torch.uint8, device=dev)
             check(L.oadg_oamix_saliency(ptr(img), H, W, ptr(self._ibox), n, spatial_ratio,
                                         ptr(self._scores_dev), ptr(self._sal_ws), nb, stream_ptr()),
                   'oadg_oamix_saliency')
-            self._scores_host = torch.empty((n,), dtype=torch.float64, pin_memory=True)
-            self._scores_host.copy_(self._scores_dev, non_blocking=True)
-            self._scores_evt = torch.cuda.Event()
-            self._scores_evt.record()
+            self._scores_copy = (staging.readback(self._scores_dev), 0, n)
 
     def _union(self):
         """union of the blurred fg masks (oa_mix.py:95-120 / bbox_augmentation.py:240-302's np.max over the masks)"""
@@ -348,7 +296,7 @@ class _ImageState:
             n = self.n
             rows = self._support_rows.reshape(n, 4)
             ok = ~self._support_empty.reshape(n) & (rows[:, 2] > 0) & (rows[:, 3] > 0)
-            self._rects = _upload(np.where(ok[:, None], rows, 0).astype(np.int32).reshape(max(n, 0), 4), self.img.device)
+            self._rects = staging.upload(np.where(ok[:, None], rows, 0).astype(np.int32).reshape(max(n, 0), 4), self.img.device)
         return self._rects
 
     def _supports(self, qbox, sxy, blur, ratio):
@@ -391,8 +339,8 @@ class _ImageState:
             if self.n == 0:
                 self._scores = []
             else:
-                self._scores_evt.synchronize()
-                self._scores = [float(s) if s >= 0 else -1 for s in self._scores_host.tolist()]
+                copy, lo, hi = self._scores_copy          # (the read-back in flight, this image's rows of it)
+                self._scores = [float(s) if s >= 0 else -1 for s in copy.wait()[lo:hi].tolist()]
         return self._scores
 
 
@@ -720,16 +668,16 @@ class OAMix:
             return
         nbytes = L.oadg_oamix_bbox_plan_bytes(n)
         deferred = self._rec is not None and PLAN_THREADS > 0 and n >= ASYNC_PLAN_MIN_BOXES
-        name = 'plan_ring' if deferred else 'ring'          # (deferred plans hold their slot until execute(): own ring)
-        ring = getattr(_TLS, name, None)
-        if ring is None:
-            ring = _PinnedRing()
-            setattr(_TLS, name, ring)
-        if deferred and self._pending_plans >= ring.SLOTS - 1:
+        if deferred and self._pending_plans >= PLAN_SLOTS - 1:
             deferred = False
-            ring = getattr(_TLS, 'ring', None) or _PinnedRing()
-            _TLS.ring = ring
-        k, buf = ring.slot(nbytes)
+        if deferred:                        # (deferred plans hold their slot until execute(): a ring of their own)
+            ring = getattr(_TLS, 'plan_ring', None)
+            if ring is None:
+                ring = _TLS.plan_ring = staging.Ring(PLAN_SLOTS, 4096)
+        else:
+            ring = staging.local_ring(st.img.device, nbytes)
+        slot = ring.reserve(nbytes)
+        buf = slot.host
         if deferred:
             lf = np.empty((n + 2,), np.int32)
         else:
@@ -751,12 +699,10 @@ class OAMix:
                 self.stats['bbox_levels'] = self.stats.get('bbox_levels', 0) + n_levels
                 self.stats['bbox_steps'] = self.stats.get('bbox_steps', 0) + n_live
             if n_live == 0:
+                slot.release()
                 return None
             used = n_live * BBOX_STEP_DTYPE.itemsize + (n_live + 1) * 4
-            dst = torch.empty((used,), dtype=torch.uint8, device=st.img.device)
-            dst.copy_(buf[:used], non_blocking=True)
-            ev = ring.events[k] = ring.events[k] or torch.cuda.Event()
-            ev.record()
+            dst = slot.commit(used, st.img.device)
             step.setdefault('keepalive', []).append(dst)          # descriptor tensor lives until the step's launches ran
             tiles_off = n_live * BBOX_STEP_DTYPE.itemsize
             return dict(dst=dst, tiles_off=tiles_off, n_live=n_live, n_levels=n_levels, work=float(9 * area.value))
@@ -886,8 +832,8 @@ class OAMix:
         tiles[1:] = np.cumsum((area + 1023) // 1024)        # one workgroup = 256 threads x 4 pixels
         dev = st.img.device
         keep = step.setdefault('keepalive', [])              # descriptor tensors live until the step's launches ran
-        steps_dev = _upload(steps.view(np.uint8).reshape(-1), dev)
-        tiles_dev = _upload(tiles, dev)
+        steps_dev = staging.upload(steps.view(np.uint8).reshape(-1), dev)
+        tiles_dev = staging.upload(tiles, dev)
         keep += [steps_dev, tiles_dev]
         from .. import hip_ops
         # model bytes of the chain (SURVEY 8d's sum 3 w h term, per blend: the rect is read, its warped source is read,
@@ -967,7 +913,7 @@ class OAMix:
             for t, (idx, rect, score) in enumerate(targets):
                 hi = 0.5 if score <= self.score_thresh else 1.0
                 tg[t] = (idx, rect, np.float32(rng.uniform(0.0, hi)))
-        tg_dev = _upload(tg.view(np.uint8).reshape(-1), st.img.device) if len(targets) else None
+        tg_dev = staging.upload(tg.view(np.uint8).reshape(-1), st.img.device) if len(targets) else None
         mean = stdinv = None
         to_rgb, dt, Hp, Wp = 0, 0, H, W
         if out_norm is not None:

@@ -12,9 +12,9 @@ from torch.profiler import record_function as _rf
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import hip_ops
+from . import hip_ops, staging
 from .core import bbox2roi, multi_apply
-from .core.bbox import DeviceSamplingResult, _pinned_to, roi_assign_sample_begin, sample_many, sample_many_begin
+from .core.bbox import DeviceSamplingResult, roi_assign_sample_begin, sample_many, sample_many_begin
 from .layers import normal_init, xavier_init
 from .losses import accuracy
 from .registry import (HEADS, ROI_EXTRACTORS, ROI_LAYERS, build_assigner, build_bbox_coder, build_head,
@@ -147,7 +147,7 @@ class BBoxHead(nn.Module):
             npos, nneg = r.pos_inds.numel(), r.neg_inds.numel()
             rows.append(torch.arange(total, total + npos))
             total += npos + nneg
-        pos_rows = _pinned_to(torch.cat(rows), dev)
+        pos_rows = staging.upload(torch.cat(rows), dev)
         like = sampling_results[0].pos_bboxes
         labels = like.new_full((total,), self.num_classes, dtype=torch.long)
         label_weights = like.new_ones(total)             # every sampled row carries weight 1 ...
@@ -296,8 +296,7 @@ class BBoxHead(nn.Module):
         if bbox_pred is not None and pos_rows is not None:
             # positives are the leading rows of every image block: their indices are known on the host
             if pos_rows.numel() > 0:
-                from .core.bbox import _pinned_to
-                pr = _pinned_to(pos_rows, bbox_pred.device)
+                pr = staging.upload(pos_rows, bbox_pred.device)
                 if self.reg_class_agnostic:
                     pos_pred = bbox_pred.view(bbox_pred.size(0), 4)[pr]
                 else:
