@@ -839,6 +839,7 @@ int oadg_roi_targets_dev(const oadg_roi_target_entry* entries_host, int n_entrie
  * [626] = the advanced state (every workgroup of the launch reads mt_state in no defined order).  Outputs: sel [B][num] int64 = per image the sorted
  * positive indices, then the sorted negative indices; counts [B][2] = k_pos, k_neg; flags [B]: bit 0 = fewer than num rows
  * sampled (the fixed-capacity layout has padding rows), bit 1 = image outside the kernel's domain (nothing sampled). */
+#define OADG_ROI_SAMPLE_MAX_IMAGES 8
 typedef struct oadg_roi_sample_image {
     const int64_t* gt_inds;
     int n;

@@ -1,11 +1,20 @@
-"""ctypes binding of liboadg_hip.so (C ABI: include/oadg_hip.h).
+"""ctypes binding of liboadg_hip.so (C ABI: include/oadg_hip.h) and the ONLY Python restatement of that header.
 
-Nothing here computes: it validates tensors, hands device pointers and the current HIP stream to the
-library and raises on any non-zero return code.  A missing library is a hard error at first use.
+Owned here: one ``ctypes.Structure`` per struct of the header (``STRUCTS``: C name -> class; field names, order and C types
+are the header's), the numpy record dtype of every table that is filled with numpy (``np.dtype(Structure)``, computed once,
+in the upper-case name next to its class), the header's constants that Python needs, and ``SIGNATURES``.  No other module
+defines a Structure, a record dtype of a header struct or a header constant.  tests/test_cabi.py parses the header and
+compares all of it - struct fields, offsets and sizes, constants, and the kind of every parameter - without a GPU.
+
+Nothing here computes: it validates tensors, hands device pointers and the current HIP stream to the library and raises on
+any non-zero return code.  A missing library is a hard error at first use.
 """
 import ctypes
 import os
-from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int64, c_long, c_size_t, c_void_p)
+from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_long, c_longlong, c_size_t,
+                    c_uint16, c_void_p)
+
+import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('OADG_HIP_LIB') or os.path.join(_HERE, 'csrc', 'liboadg_hip.so')   # (override: A/B probes)
@@ -52,6 +61,8 @@ class RoiSampleImage(Structure):
 
 
 ROI_SAMPLE_MAX_IMAGES = 8
+RPN_MAX_LEVELS = 8
+PARSE_LOSSES_MAX = 32
 
 
 class RegionOp(Structure):
@@ -61,6 +72,70 @@ class RegionOp(Structure):
 
 OP_COPY, OP_LUT_AUTOCONTRAST, OP_LUT_EQUALIZE, OP_POSTERIZE, OP_SOLARIZE, OP_IMAGE, OP_BG_WARP, OP_WARP_NEG = range(8)
 OP_ENH_BRIGHTNESS, OP_ENH_COLOR, OP_ENH_CONTRAST, OP_ENH_SHARPNESS = 8, 9, 10, 11
+CORRUPT_NEAREST, CORRUPT_REFLECT, CORRUPT_MIRROR = 0, 1, 2
+CORRUPT_TO_U8_CLIP, CORRUPT_TO_U8, CORRUPT_TO_F32 = 0, 1, 2
+CORRUPT_BRIGHTNESS, CORRUPT_SATURATE = 0, 1
+
+
+# ---- the tables that are filled with numpy: Structure + its record dtype (pointer fields come out as uint64) ----------------
+def _f(ctype, names):
+    return [(n, ctype) for n in names.split()]
+
+
+class ColsumJob(Structure):   # oadg_colsum_job
+    _fields_ = _f(vp, 'part out dgamma mean var') + _f(ci, 'rows K first_block') + [('eps', cf)]
+
+
+class WgradJob(Structure):   # oadg_wgrad_job
+    _fields_ = _f(vp, 'x dy part') + [('P', cl)] + _f(ci, 'N H W C K R S stride pad dil Ho Wo splits chunks_per_split '
+                                                          'first_block blocks strip_rows pad_')
+
+
+class PrepBwdJob(Structure):   # oadg_prep_bwd_job
+    _fields_ = _f(vp, 'part gbias w scale mean var dw dgamma') + [('eps', cf)] + _f(ci, 'splits K C R S w_krsc first_block')
+
+
+class PrepDesc(Structure):   # oadg_prep_desc
+    _fields_ = _f(vp, 'w gamma beta mean var bias_in wf wt bias scale') + [('eps', cf)] + \
+        _f(ci, 'K C R S w_krsc wt_mode first_block')
+
+
+class SelectJob(Structure):   # oadg_select_job
+    _fields_ = [('gt_inds', vp), ('n', cl)] + _f(ci, 'mode k all rank_off') + [('out_off', cl)]
+
+
+class SgdTensor(Structure):   # oadg_sgd_tensor
+    _fields_ = _f(vp, 'param grad momentum') + _f(c_longlong, 'numel first_block') + _f(ci, 'first_step pad')
+
+
+class MixTarget(Structure):   # oadg_mix_target
+    _fields_ = [('fg_index', ci), ('rect', ci * 4), ('m_oa', cf)]
+
+
+class BboxStep(Structure):   # oadg_bbox_step
+    _fields_ = [('minv', cd * 6), ('rect', ci * 4), ('row', ci), ('pad_', ci), ('scratch_off', c_longlong)]
+
+
+class BboxChain(Structure):   # oadg_bbox_chain
+    _fields_ = _f(vp, 'img steps_dev tile_prefix_dev level_first_host tile_prefix_host My Mx scratch') + \
+        _f(ci, 'H W n_levels pad_')
+
+
+class JpegDesc(Structure):   # oadg_jpeg_desc (filled by oadg_jpeg_entropy_decode: Python only needs its size)
+    _fields_ = _f(c_int32, 'height width ncomp hmax vmax mcux mcuy reserved') + _f(c_int32 * 4, 'h v bw bh cw ch') + \
+        [('off', c_int64 * 4), ('qt', c_uint16 * 64 * 4)]
+
+
+COLSUM_JOB, WGRAD_JOB, PREP_BWD_JOB, PREP_DESC, SELECT_JOB, SGD_TENSOR, MIX_TARGET, BBOX_STEP, BBOX_CHAIN = (
+    np.dtype(c) for c in (ColsumJob, WgradJob, PrepBwdJob, PrepDesc, SelectJob, SgdTensor, MixTarget, BboxStep, BboxChain))
+
+STRUCTS = {   # every struct of the header, by its C name
+    'oadg_rpn_level': RpnLevel, 'oadg_rpn_loss_level': RpnLossLevel, 'oadg_roi_assign_image': RoiAssignImage,
+    'oadg_roi_target_entry': RoiTargetEntry, 'oadg_roi_sample_image': RoiSampleImage, 'oadg_region_op': RegionOp,
+    'oadg_colsum_job': ColsumJob, 'oadg_wgrad_job': WgradJob, 'oadg_prep_bwd_job': PrepBwdJob, 'oadg_prep_desc': PrepDesc,
+    'oadg_select_job': SelectJob, 'oadg_sgd_tensor': SgdTensor, 'oadg_mix_target': MixTarget, 'oadg_bbox_step': BboxStep,
+    'oadg_bbox_chain': BboxChain, 'oadg_jpeg_desc': JpegDesc,
+}
 
 # name -> (restype, argtypes); must list every symbol include/oadg_hip.h declares
 SIGNATURES = {

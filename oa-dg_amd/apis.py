@@ -177,10 +177,6 @@ def pin_rank_to_cores(local_rank, world, cores_per_rank=8):
             f'(rank {local_rank}: CPUs {mine[0]}-{mine[-1]})')
 
 
-_SGD_TENSOR = np.dtype([('param', np.uint64), ('grad', np.uint64), ('momentum', np.uint64), ('numel', np.int64),
-                        ('first_block', np.int64), ('first_step', np.int32), ('pad', np.int32)])      # oadg_sgd_tensor
-
-
 def _same_layout(a, b):
     """equal strides on every dimension that has more than one element (a size-1 dimension's stride is arbitrary:
     a [K, C, 1, 1] channels_last weight and its gradient need not agree there)"""
@@ -245,7 +241,7 @@ class FusedSGD(torch.optim.SGD):
             key = (gi, tuple((id(p), p.numel()) for p in ps))
             ent = self._tables.get(gi)
             if ent is None or ent['key'] != key:
-                tab = np.zeros(len(ps), dtype=_SGD_TENSOR)
+                tab = np.zeros(len(ps), dtype=_lib.SGD_TENSOR)
                 blocks = 0
                 for i, p in enumerate(ps):
                     tab[i]['numel'], tab[i]['first_block'] = p.numel(), blocks

@@ -407,10 +407,6 @@ class RandomSampler:
         return SamplingResult(pos_inds, neg_inds, bboxes, gt_bboxes, assign_result, gt_flags)
 
 
-_JOB_DTYPE = np.dtype([('gt_inds', np.uint64), ('n', np.int64), ('mode', np.int32), ('k', np.int32),
-                       ('all', np.int32), ('rank_off', np.int32), ('out_off', np.int64)])      # oadg_select_job
-
-
 class PendingSampling:
     """RandomSampler.sample for a list of images, split in two so that the single device->host read never
     stalls the stream: :func:`sample_many_begin` enqueues the candidate masks and an asynchronous copy of the
@@ -459,7 +455,7 @@ class PendingSampling:
         """Locate the planned candidates with csrc/targets.hip (two launches for the whole batch)."""
         from .. import _lib
         nj = 2 * len(plan)
-        jobs = np.zeros(nj, dtype=_JOB_DTYPE)
+        jobs = np.zeros(nj, dtype=_lib.SELECT_JOB)
         ranks, out_off, max_n = [], 0, 0
         for i, (k_pos, r_pos, k_neg, r_neg) in enumerate(plan):
             gi = self.prepared[i][0].gt_inds

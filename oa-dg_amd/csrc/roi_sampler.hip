@@ -24,7 +24,7 @@
 namespace {
 
 constexpr int RS_MAXN = 4096;          // rows (gts + proposals) per image the LDS arrays hold
-constexpr int RS_MAX_IMAGES = 8;
+constexpr int RS_MAX_IMAGES = OADG_ROI_SAMPLE_MAX_IMAGES;
 constexpr int MT_N = 624, MT_M = 397;
 
 struct RoiSampleArgs {

@@ -507,7 +507,7 @@ class RPNHead(AnchorHead):
         coder = self.bbox_coder
         dev = cls_scores[0].device
         if not (self.FUSED_PROPOSALS and dev.type == 'cuda' and self.use_sigmoid_cls and type(coder) is DeltaXYWHBBoxCoder
-                and not coder.add_ctr_clamp and len(cls_scores) <= 8 and n_img >= 1):
+                and not coder.add_ctr_clamp and len(cls_scores) <= _lib.RPN_MAX_LEVELS and n_img >= 1):
             return None
         nms_cfg = dict(cfg.nms)
         if nms_cfg.pop('type', 'nms') != 'nms':

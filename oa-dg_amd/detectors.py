@@ -209,7 +209,7 @@ class BaseDetector(nn.Module):
     def _parse_losses_fused(losses):
         """(loss, packed log vector, names) from one launch (hip_ops.parse_losses) when every value is a one-element fp32
         CUDA tensor (a mean of one element is the element; the sums are python's left-to-right adds) - else None"""
-        from . import hip_ops
+        from . import _lib, hip_ops
         if not hip_ops.FUSED_PARSE_LOSSES or 'loss' in losses:
             return None
         vals, name_of, names, mask = [], [], [], 0
@@ -225,7 +225,7 @@ class BaseDetector(nn.Module):
             if 'loss' in name:
                 mask |= 1 << len(names)
             names.append(name)
-        if not vals or len(vals) > 32 or len(names) > 30:
+        if not vals or len(vals) > _lib.PARSE_LOSSES_MAX or len(names) > 30:
             return None
         loss, packed = hip_ops.parse_losses(vals, name_of, len(names), mask)
         return loss, packed, names + ['loss']

@@ -6,6 +6,7 @@ Forward, data gradients (stride 1 and 2) and weight gradients run on the hand-wr
 """
 import ctypes
 import os
+import weakref
 
 import numpy as np
 import torch
@@ -142,11 +143,6 @@ def _close_shared_leftovers():
     _SHARED_OPEN.clear()
 
 
-_CS_JOB = np.dtype([('part', np.uint64), ('out', np.uint64), ('dgamma', np.uint64), ('mean', np.uint64),
-                    ('var', np.uint64), ('rows', np.int32), ('K', np.int32), ('first_block', np.int32),
-                    ('eps', np.float32)])                                                           # oadg_colsum_job
-
-
 class _PendingColsum:
     __slots__ = ('part', 'out', 'fix', 'done', 'targets')
 
@@ -193,7 +189,7 @@ def flush_colsums():
     if not pend:
         return 0
     dev = pend[0].out.device
-    tab = np.zeros(len(pend), dtype=_CS_JOB)
+    tab = np.zeros(len(pend), dtype=_lib.COLSUM_JOB)
     blocks = 0
     for i, e in enumerate(pend):
         K = e.out.shape[0]
@@ -232,19 +228,11 @@ _WQ = []
 _WQ_WORK = 0
 SHARED_GROUP = os.environ.get('OADG_WGRAD_SHARED', '1') == '1'      # the uses of a shared weight as ONE grouped launch
 _SHARED_OPEN = set()        # bank entries holding jobs of a shared weight whose last use has not arrived yet
-_WG_JOB = np.dtype([('x', 'u8'), ('dy', 'u8'), ('part', 'u8'), ('P', 'i8'), ('N', 'i4'), ('H', 'i4'), ('W', 'i4'),
-                    ('C', 'i4'), ('K', 'i4'), ('R', 'i4'), ('S', 'i4'), ('stride', 'i4'), ('pad', 'i4'), ('dil', 'i4'),
-                    ('Ho', 'i4'), ('Wo', 'i4'), ('splits', 'i4'), ('cps', 'i4'), ('first_block', 'i4'),
-                    ('blocks', 'i4'), ('strip_rows', 'i4'), ('pad_', 'i4')], align=True)            # oadg_wgrad_job
-_PB_JOB = np.dtype([('part', 'u8'), ('gbias', 'u8'), ('w', 'u8'), ('scale', 'u8'), ('mean', 'u8'), ('var', 'u8'),
-                    ('dw', 'u8'), ('dgamma', 'u8'), ('eps', 'f4'), ('splits', 'i4'), ('K', 'i4'), ('C', 'i4'),
-                    ('R', 'i4'), ('S', 'i4'), ('w_krsc', 'i4'), ('first_block', 'i4')], align=True)  # oadg_prep_bwd_job
-assert _WG_JOB.itemsize == 104 and _PB_JOB.itemsize == 96
 
 
 # host table -> device memory without a blocking copy (weight-gradient jobs, BN-fold consumer jobs, column-sum jobs): a slot
 # whose last copy is still queued is stepped around, not waited for
-_STAGE = staging.Ring(16, 64 * _WG_JOB.itemsize, grow_when_busy=True)
+_STAGE = staging.Ring(16, 64 * ctypes.sizeof(_lib.WgradJob), grow_when_busy=True)
 
 
 def wgrad_work(N, Ho, Wo, C, K, R, S):
@@ -288,7 +276,7 @@ def wgrad_multi(jobs, target_blocks=256):
     """[(x16, gy16, K, R, S, stride, pad, dil)] -> (workspace, [(part pointer, splits)] per job): the weight gradients of
     several layers as fp32 split partials from ONE launch (csrc oadg_conv2d_wgrad_multi)"""
     L = _lib.lib()
-    tab = np.zeros(len(jobs), dtype=_WG_JOB)
+    tab = np.zeros(len(jobs), dtype=_lib.WGRAD_JOB)
     dev = jobs[0][0].device
     for r, (x16, gy16, K, R, S, stride, pad, dil) in zip(tab, jobs):
         N, C, H, W = x16.shape
@@ -357,7 +345,7 @@ def flush_wgrads():
             assert jobs[i + m].prep is None and jobs[i + m].geo[3:7] == j.geo[3:7]
             splits += parts[i + m][1]
         cons.append((j, pp, splits))
-    tab = np.zeros(len(cons), dtype=_PB_JOB)
+    tab = np.zeros(len(cons), dtype=_lib.PREP_BWD_JOB)
     first, max_crs = 0, 0
     p_ = lambda t: 0 if t is None else t.data_ptr()  # noqa: E731
     for r, (j, pp, splits) in zip(tab, cons):
@@ -849,7 +837,6 @@ class _Bank:
     """All bank entries of the process + the device descriptor table of oadg_prep_conv_weights_multi."""
 
     def __init__(self):
-        import weakref
         self.entries = weakref.WeakSet()
         self.table = None            # (device tensor, [entries in table order], total blocks)
         self.dirty = True
@@ -861,8 +848,6 @@ class _Bank:
 
     def refresh(self):
         """re-prepare every registered layer whose parameters changed, in ONE launch; returns the number of layers"""
-        import numpy as np
-        import weakref
         ents = []
         for e in self.entries:
             if e.args is None or not e.args[0].is_cuda:
@@ -881,11 +866,7 @@ class _Bank:
             return 0
         if self.dirty or self.table is None or len(self.table[1]) != len(ents) or any(r() is None for r in self.table[1]):
             ents.sort(key=lambda e: e.wf.data_ptr())
-            dt = np.dtype([('w', 'u8'), ('gamma', 'u8'), ('beta', 'u8'), ('mean', 'u8'), ('var', 'u8'), ('bias_in', 'u8'),
-                           ('wf', 'u8'), ('wt', 'u8'), ('bias', 'u8'), ('scale', 'u8'), ('eps', 'f4'), ('K', 'i4'),
-                           ('C', 'i4'), ('R', 'i4'), ('S', 'i4'), ('w_krsc', 'i4'), ('wt_mode', 'i4'),
-                           ('first_block', 'i4')], align=True)
-            tab = np.zeros((len(ents),), dt)
+            tab = np.zeros((len(ents),), _lib.PREP_DESC)
             p_ = lambda t: 0 if t is None else t.data_ptr()  # noqa: E731
             first = 0
             for i, e in enumerate(ents):

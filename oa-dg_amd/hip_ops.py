@@ -663,7 +663,7 @@ def nms_sorted_batched(boxes, counts, iou_thr, max_keep=-1):
     return keep, keep_cnt
 
 
-JPEG_DESC_BYTES = 672      # sizeof(oadg_jpeg_desc), include/oadg_hip.h
+JPEG_DESC_BYTES = ctypes.sizeof(_lib.JpegDesc)
 
 
 def jpeg_pixels_bgr(coef, desc, out, slot, planes=None):
@@ -693,8 +693,7 @@ def jpeg_pixels_bgr(coef, desc, out, slot, planes=None):
 # --------------------------------------------------------------------------------------- robustness-benchmark corruptions
 # csrc/corrupt.hip: the device half of pipelines/corrupt.py's Corrupt.batch (pipelines/corrupt_device.py builds the
 # draws, weights and tables on the host and calls these on torch's current stream)
-CORRUPT_MODES = dict(nearest=0, reflect=1, mirror=2)
-CORRUPT_TO_U8_CLIP, CORRUPT_TO_U8, CORRUPT_TO_F32 = 0, 1, 2
+CORRUPT_MODES = dict(nearest=_lib.CORRUPT_NEAREST, reflect=_lib.CORRUPT_REFLECT, mirror=_lib.CORRUPT_MIRROR)
 
 
 def _dense(t, dtype, what):
@@ -731,7 +730,7 @@ def corrupt_epilogue(src, dst, kind, scale=1.0):
     """float64 -> uint8(clip(x, 0, 1) * 255) / uint8(x * 255) / float32(x * scale), element by element"""
     require_cuda(src, dst)
     _dense(src, torch.float64, 'src')
-    _dense(dst, torch.float32 if kind == CORRUPT_TO_F32 else torch.uint8, 'dst')
+    _dense(dst, torch.float32 if kind == _lib.CORRUPT_TO_F32 else torch.uint8, 'dst')
     if dst.numel() != src.numel():
         raise ValueError('src / dst sizes differ')
     check(_lib.lib().oadg_corrupt_epilogue(ptr(src), ptr(dst), src.numel(), int(kind), float(scale), stream_ptr()),

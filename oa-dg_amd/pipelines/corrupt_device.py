@@ -87,7 +87,7 @@ def _gaussian_blur(x, severity):
     lut, = _upload(x.device, _LUT64)
     blurred = _separable(x, gaussian_weights(c, 4.0), 'nearest', lut)
     out = torch.empty_like(x)
-    hip_ops.corrupt_epilogue(blurred, out, hip_ops.CORRUPT_TO_U8_CLIP)
+    hip_ops.corrupt_epilogue(blurred, out, _lib.CORRUPT_TO_U8_CLIP)
     return out
 
 
@@ -99,7 +99,7 @@ def _glass_blur(x, severity):
     lut, = _upload(x.device, _LUT64)
     STATS['host_s'] += time.perf_counter() - t0
     mid = torch.empty_like(x)
-    hip_ops.corrupt_epilogue(_separable(x, wts, 'nearest', lut), mid, hip_ops.CORRUPT_TO_U8)
+    hip_ops.corrupt_epilogue(_separable(x, wts, 'nearest', lut), mid, _lib.CORRUPT_TO_U8)
     host = mid.cpu().numpy()
     t0 = time.perf_counter()
     if h > 2 * delta and w > 2 * delta:
@@ -112,7 +112,7 @@ def _glass_blur(x, severity):
     shuffled, lut = _upload(x.device, host, _LUT64)
     STATS['host_s'] += time.perf_counter() - t0
     out = torch.empty_like(x)
-    hip_ops.corrupt_epilogue(_separable(shuffled, wts, 'nearest', lut), out, hip_ops.CORRUPT_TO_U8_CLIP)
+    hip_ops.corrupt_epilogue(_separable(shuffled, wts, 'nearest', lut), out, _lib.CORRUPT_TO_U8_CLIP)
     return out
 
 
@@ -194,7 +194,7 @@ def _elastic_transform(x, severity):
     fields = []
     for k in range(2):
         f = torch.empty((N, h, w), dtype=torch.float32, device=x.device)
-        hip_ops.corrupt_epilogue(_separable_2(dev[k], w0, w1, 'reflect'), f, hip_ops.CORRUPT_TO_F32, alpha)
+        hip_ops.corrupt_epilogue(_separable_2(dev[k], w0, w1, 'reflect'), f, _lib.CORRUPT_TO_F32, alpha)
         fields.append(f)
     out = torch.empty_like(x)
     hip_ops.corrupt_elastic(x, fields[0], fields[1], out, lut)
@@ -205,7 +205,7 @@ def _brightness(x, severity):
     c = [.1, .2, .3, .4, .5][severity - 1]
     lut, = _upload(x.device, _LUT64)
     out = torch.empty_like(x)
-    hip_ops.corrupt_hsv(x, out, 0, c, 0.0, lut)
+    hip_ops.corrupt_hsv(x, out, _lib.CORRUPT_BRIGHTNESS, c, 0.0, lut)
     return out
 
 
@@ -213,7 +213,7 @@ def _saturate(x, severity):
     c = [(0.3, 0), (0.1, 0), (2, 0), (5, 0.1), (20, 0.2)][severity - 1]
     lut, = _upload(x.device, _LUT64)
     out = torch.empty_like(x)
-    hip_ops.corrupt_hsv(x, out, 1, c[0], c[1], lut)
+    hip_ops.corrupt_hsv(x, out, _lib.CORRUPT_SATURATE, c[0], c[1], lut)
     return out
 
 

@@ -50,12 +50,6 @@ AUG_LISTS = {   # oa_mix.py:15-29
                    'brightness', 'sharpness', 'bboxes_only_rotate', 'bboxes_only_shear_xy',
                    'bboxes_only_translate_xy', 'bg_only_rotate', 'bg_only_shear_xy', 'bg_only_translate_xy'],
 }
-MIX_TARGET_DTYPE = np.dtype([('fg_index', '<i4'), ('rect', '<i4', (4,)), ('m_oa', '<f4')])   # oadg_mix_target
-BBOX_STEP_DTYPE = np.dtype([('minv', '<f8', (6,)), ('rect', '<i4', (4,)), ('row', '<i4'), ('pad_', '<i4'),
-                            ('scratch_off', '<i8')])                                          # oadg_bbox_step
-BBOX_CHAIN_DTYPE = np.dtype([('img', '<u8'), ('steps_dev', '<u8'), ('tile_prefix_dev', '<u8'), ('level_first_host', '<u8'),
-                             ('tile_prefix_host', '<u8'), ('My', '<u8'), ('Mx', '<u8'), ('scratch', '<u8'), ('H', '<i4'),
-                             ('W', '<i4'), ('n_levels', '<i4'), ('pad_', '<i4')])                        # oadg_bbox_chain
 LOCKSTEP = os.environ.get('OADG_OAMIX_LOCKSTEP', '1') == '1'    # the images of a batch advance their per-box chains together
 LANES = int(os.environ.get('OADG_OAMIX_LANES', '3'))    # buffer sets per image inside the lockstep pass (one per mixture
                                                         # chain; 1: the chains share a set and follow each other)
@@ -469,7 +463,7 @@ class OAMix:
             if not batch:
                 assert left == 0, 'OA-Mix command graph did not drain'
                 break
-            tab = np.zeros((len(batch),), BBOX_CHAIN_DTYPE)
+            tab = np.zeros((len(batch),), _lib.BBOX_CHAIN)
             work = 0.0
             for r, (_, _, c) in zip(tab, batch):
                 r['img'], r['steps_dev'], r['tile_prefix_dev'] = c['img'], c['steps_dev'], c['tile_prefix_dev']
@@ -701,10 +695,10 @@ class OAMix:
             if n_live == 0:
                 slot.release()
                 return None
-            used = n_live * BBOX_STEP_DTYPE.itemsize + (n_live + 1) * 4
+            used = n_live * _lib.BBOX_STEP.itemsize + (n_live + 1) * 4
             dst = slot.commit(used, st.img.device)
             step.setdefault('keepalive', []).append(dst)          # descriptor tensor lives until the step's launches ran
-            tiles_off = n_live * BBOX_STEP_DTYPE.itemsize
+            tiles_off = n_live * _lib.BBOX_STEP.itemsize
             return dict(dst=dst, tiles_off=tiles_off, n_live=n_live, n_levels=n_levels, work=float(9 * area.value))
 
         def chain_rec(f):
@@ -813,7 +807,7 @@ class OAMix:
                                        minvs.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), n, H, W,
                                        level.ctypes.data_as(ctypes.POINTER(ctypes.c_int))), 'oadg_oamix_bbox_levels')
         order = np.argsort(level, kind='stable')
-        steps = np.zeros((n,), BBOX_STEP_DTYPE)
+        steps = np.zeros((n,), _lib.BBOX_STEP)
         steps['minv'] = np.asarray(minvs, np.float64)[order]
         steps['rect'] = np.asarray(rects, np.int32)[order]
         steps['row'] = np.asarray(rows, np.int32)[order]
@@ -901,7 +895,7 @@ class OAMix:
             targets.append((-1, tuple(int(v) for v in bx), sc))
         # object_aware_mixing (oa_mix.py:281-309)
         m = rng.beta(self.aug_prob_coeff, self.aug_prob_coeff)
-        tg = np.zeros((len(targets),), MIX_TARGET_DTYPE)
+        tg = np.zeros((len(targets),), _lib.MIX_TARGET)
         if len(targets) >= MIX_TILES_MIN_TARGETS:
             # the targets' mixing weights in one draw: uniform(0, hi) = 0.0 + (hi - 0.0) * next_double() per target
             # (numpy's legacy uniform), i.e. the next len(targets) doubles of the stream in target order

@@ -6,7 +6,7 @@ import ctypes
 import numpy as np
 import pytest
 
-from oadg_amd import _lib, hip_conv
+from oadg_amd import _lib
 
 LAYER4 = [(8, 64, 128, 1024, 256, 1, 1, 0), (8, 32, 64, 2048, 256, 1, 1, 0), (8, 32, 64, 512, 2048, 1, 1, 0),
           (8, 32, 64, 512, 512, 3, 1, 1), (8, 32, 64, 2048, 512, 1, 1, 0), (8, 32, 64, 512, 2048, 1, 1, 0),
@@ -22,7 +22,7 @@ def _plan(group, target=256):
         L = _lib.lib()
     except Exception as e:                     # the library is built by __graft_entry__.build(); without it nothing to test
         pytest.skip(f'liboadg_hip.so not built: {e}')
-    tab = np.zeros(len(group), dtype=hip_conv._WG_JOB)
+    tab = np.zeros(len(group), dtype=_lib.WGRAD_JOB)
     for r, (N, H, W, C, K, R, stride, pad) in zip(tab, group):
         r['N'], r['H'], r['W'], r['C'], r['K'], r['R'], r['S'] = N, H, W, C, K, R, R
         r['stride'], r['pad'], r['dil'] = stride, pad, 1
@@ -36,7 +36,7 @@ def _entries(tab):
     for r in tab:
         tiles = (r['K'] // 256) * (r['C'] // 256) * r['R'] * r['S']
         n = (r['P'] + 63) // 64
-        out += [min(int(r['cps']), int(n - s * r['cps'])) for s in range(r['splits']) for _ in range(tiles)]
+        out += [min(int(r['chunks_per_split']), int(n - s * r['chunks_per_split'])) for s in range(r['splits']) for _ in range(tiles)]
     return out
 
 
@@ -59,8 +59,8 @@ def test_plan_covers_every_job_and_slices_the_list(name, group):
     for r in tab:
         tiles = (r['K'] // 256) * (r['C'] // 256) * r['R'] * r['S']
         n = (r['P'] + 63) // 64
-        assert r['splits'] >= 1 and r['cps'] >= 1
-        assert r['splits'] * r['cps'] >= n > (r['splits'] - 1) * r['cps']          # every pixel chunk once, no empty split
+        assert r['splits'] >= 1 and r['chunks_per_split'] >= 1
+        assert r['splits'] * r['chunks_per_split'] >= n > (r['splits'] - 1) * r['chunks_per_split']          # every pixel chunk once, no empty split
         assert r['first_block'] == first and r['blocks'] == tiles * r['splits']
         first += r['blocks']
     assert first == total == len(_entries(tab))
