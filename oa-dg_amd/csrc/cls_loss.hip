@@ -118,10 +118,12 @@ __global__ void sm_kernel(const float* __restrict__ x, const int64_t* __restrict
         }
         m1 = wave_max(m1);
         m2 = wave_max(m2);
-        float s1 = 0.f, s2 = 0.f;
+        const int64_t lab = labels[r];
+        float s1 = 0.f, s2 = 0.f, dlab = 0.f;
 #pragma unroll
         for (int k = 0; k < MAXC_PER_LANE; ++k) {
             const int c = lane + 64 * k;
+            if (!BWD && c < C && c == (int)lab) dlab = a1[k] - m1;  // x_label - max, kept from before the exponential
             a1[k] = c < C ? expf(a1[k] - m1) : 0.f;
             a2[k] = c < C ? expf(a2[k] - m2) : 0.f;
             s1 += a1[k];
@@ -129,10 +131,9 @@ __global__ void sm_kernel(const float* __restrict__ x, const int64_t* __restrict
         }
         s1 = wave_sum(s1);
         s2 = wave_sum(s2);
-        const int64_t lab = labels[r];
         const bool valid = lab != IGNORE_INDEX && lab >= 0 && lab < C;
         const float w = valid ? (weights ? weights[r] : 1.f) : 0.f;
-        float jrow = 0.f, dot1 = 0.f, dot2 = 0.f, plab = 0.f;
+        float jrow = 0.f, dot1 = 0.f, dot2 = 0.f;
         float gd1[MAXC_PER_LANE], gd2[MAXC_PER_LANE];
 #pragma unroll
         for (int k = 0; k < MAXC_PER_LANE; ++k) {
@@ -145,7 +146,6 @@ __global__ void sm_kernel(const float* __restrict__ x, const int64_t* __restrict
                 const float mr = (p1 + p2) / 2.0f;
                 const float m = fminf(fmaxf(mr, 1e-7f), 1.0f);
                 const float lm = logf(m);
-                if (c == (int)lab) plab = p1;
                 if (!BWD) {
                     jrow += (xlogy_term(p1, lm) + xlogy_term(p2, lm)) / 2.0f;
                 } else {
@@ -158,11 +158,13 @@ __global__ void sm_kernel(const float* __restrict__ x, const int64_t* __restrict
         }
         if (!BWD) {
             jrow = wave_sum(jrow);
-            plab = wave_sum(plab);  // exactly one lane holds it
+            dlab = wave_sum(dlab);  // exactly one lane holds it (the others add 0)
             if (lane == 0) {
                 js += (double)jrow;
-                // F.cross_entropy = -log_softmax[label]; log p = (x - m) - log s
-                if (valid) ce += (double)(w * -logf(plab));
+                // F.cross_entropy = -log_softmax[label] = log s - (x_label - m): never through the label's probability,
+                // which is a denormal from a gap of 87 between the row maximum and the label's logit and 0 from 104
+                // (-logf of it: wrong digits, then +inf where the reference's log-softmax gives the gap itself)
+                if (valid) ce += (double)(w * (logf(s1) - dlab));
             }
         } else {
             dot1 = wave_sum(dot1);

@@ -28,6 +28,16 @@ GAMMA_ROI = 2.0 ** -16
 # fp32 arithmetic of the loss kernels (logf / expf, per-element terms summed in fp64, the final fp32 scalings).  Set from
 # measurement: the worst err / bound of the fp32 outputs over the three audited steps is 0.072 (supcon's feature gradient,
 # configs[1]), a margin of 14x; the loss values stay below 0.006, sig_kernel<true> / sm_kernel<true> below 0.008.
+# At saturated operands (tests/test_loss_stress.py: softmax gaps up to 300, sigmoid logits N(0, 200) and the values around
+# the 1e-7 clamp and expf's underflow, deltas up to 1e4, supcon duplicates / antipodes / zero rows / norms over six decades)
+# the same constants hold on the MI355X with no named term added - worst err / bound of the fp32 outputs:
+#   sig_kernel<true> 0.093, rpn_loss_bwd_kernel fp32 maps 0.096 (<true, 0> 0.091, <false, 0> 0.096), sm_kernel<true> 0.039,
+#   supcon_bwd_fin_kernel 0.039, roi_reg_bwd_kernel 0.008; the loss values: sm_kernel<false> 0.019 (one pair alone; 0.007
+#   for the whole launch and under one-row weights), sig_kernel<false> 0.002, rpn_loss_fwd_kernel 0.001,
+#   roi_reg_acc_fwd_kernel 0.004, supcon_fin_kernel 0.003, parse_losses_kernel 0.004.
+# (bf16 outputs - the RPN gradient maps, the bf16 box gradient - reach 0.82 - 0.97 there as in the audited steps: RHO.)
+# sm_kernel<false> computed the CE as -logf(p_label) until that suite: +inf from a gap of 104 between the row maximum and the
+# label's logit, a one-unit denormal at 103 (91 - 131 bounds of that row), NaN as soon as such a row had weight 0.
 GAMMA_LOSS = 2.0 ** -16
 ALPHA = 1e-30
 # the RoI head's weight gradients: the library GEMM (g^T x, K = up to 4096 bf16 products summed in fp32) - not this
