@@ -200,6 +200,180 @@ def colsum_expect(y_nhwc):
     return y.sum(0), y.abs().sum(0)
 
 
+# ------------------------------------------------------------------------------------------- the integer-exact regime
+# Operands that are small integers stored in bf16 (bias: fp32 integers): every product is exact in fp32 and so is every
+# partial sum in ANY order while S - the same computation over absolute values - stays below 2^24.  A kernel then has
+# exactly one admissible output: the fp64 integer for fp32 outputs, its round-to-nearest-even bf16 value for bf16 ones
+# (tests/test_conv_stress.py).  The roundings are restated on the bit pattern, not taken from torch's cast.
+EXACT_LIMIT = 2.0 ** 24
+
+
+def _bits(t):
+    """int32 bit patterns of fp64 values that are exact in fp32 (asserted)"""
+    f = t.to(torch.float32)
+    assert torch.equal(f.to(torch.float64), t.to(torch.float64)), 'value not exact in fp32'
+    return f.contiguous().view(torch.int32)
+
+
+def _unbits(b):
+    return b.view(torch.float32).to(torch.float64)
+
+
+def bf16_rne(t):
+    """fp64 (exact in fp32) -> fp64 of its bf16 value, round to nearest, ties to even: bits + 0x7fff + (bit 16)"""
+    b = _bits(t)
+    return _unbits((b + 0x7fff + ((b >> 16) & 1)) & -65536)
+
+
+def bf16_trunc(t):
+    """the conversion that drops the low 16 bits (round towards zero): what RHO = 2^-8 would still admit"""
+    return _unbits(_bits(t) & -65536)
+
+
+def bf16_half_away(t):
+    """round to nearest, ties away from zero: bits + 0x8000"""
+    return _unbits((_bits(t) + 0x8000) & -65536)
+
+
+def bf16_ties(t, live=None):
+    """(down, up): how many elements are exact bf16 ties (low 16 bits 0x8000) that nearest-even rounds down / up in
+    magnitude, among the ``live`` elements (those whose rounding reaches the stored output)"""
+    b = _bits(t)
+    tie = (b & 0xffff) == 0x8000
+    if live is not None:
+        tie = tie & live
+    odd = ((b >> 16) & 1) == 1
+    return int((tie & ~odd).sum()), int((tie & odd).sum())
+
+
+def _keep(shape, mask, mask_bits):
+    keep = None
+    if mask is not None:
+        keep = _nhwc64(mask) > 0
+    if mask_bits is not None:
+        kb = unpack_bits(mask_bits, shape)
+        keep = kb if keep is None else keep & kb
+    return keep
+
+
+def forward_exact(x, w, bias, residual, stride, pad, dil, relu, mask=None, mask_bits=None, res_up=False):
+    """conv_forward's contract on integer operands: (y [N,Ho,Wo,K] fp64 - the ONE admissible stored output, S, first, live).
+    ``first`` = conv + bias, the fp32 value of the first rounding; without a residual y = relu(rne(first)), with one
+    y = rne(relu(rne(first) + res)) (csrc finish_piece: the bf16 tile, then the sum rounded again); then mask and bits.
+    ``live``: the elements whose first rounding reaches the output (not masked, not cut by the ReLU)."""
+    r, S = conv_ref(x, w, stride, pad, dil)
+    if bias is not None:
+        b64 = bias.detach().to(torch.float64)
+        r = r + b64
+        S = S + b64.abs()
+    first = r
+    y = bf16_rne(r)
+    if residual is not None:
+        res = _nhwc64(residual)
+        if res_up:
+            res = res.repeat_interleave(2, 1).repeat_interleave(2, 2)
+        S = S + res.abs()
+        t = y + res
+        y = bf16_rne(t.clamp_min(0) if relu else t)
+    elif relu:
+        y = y.clamp_min(0)
+    live = (y != 0) if relu else torch.ones_like(y, dtype=torch.bool)
+    keep = _keep(y.shape, mask, mask_bits)
+    if keep is not None:
+        y = y * keep
+        live = live & keep
+    return y, S, first, live
+
+
+def dgrad_s2_exact(gy, w, H, W, pad, acc0=None, mask=None, mask_bits=None):
+    """conv_dgrad_s2's contract on integer operands: (dx [N,H,W,C] fp64, S, first, live); ``acc0``: the deposit the launch
+    adds in place (rne(rne(conv) + acc0))"""
+    r, S = dgrad_s2_ref(gy, w, H, W, pad)
+    first = r
+    y = bf16_rne(r)
+    if acc0 is not None:
+        a = _nhwc64(acc0)
+        S = S + a.abs()
+        y = bf16_rne(y + a)
+    live = torch.ones_like(y, dtype=torch.bool)
+    keep = _keep(y.shape, mask, mask_bits)
+    if keep is not None:
+        y = y * keep
+        live = keep
+    return y, S, first, live
+
+
+def wgrad_split_geometry(L, N, Ho, Wo, C, K, R, S_, splits):
+    """pixels per split of a single-layer weight-gradient launch that returned ``splits`` partials: csrc wgrad_launch -
+    ``chunks_per_split = ceil(nchunks / splits)`` 64-pixel chunks (conv_mfma.hip, `a.chunks_per_split = ...`), and for
+    the 256-tile kernel on filters with taps and Wo % 64 == 0 whole output rows (wgrad_strip: per = ceil(N Ho / splits0)
+    rows, splits = ceil(N Ho / per), splits0 = max(1, 256 / weight tiles) from wgrad256_splits).  Split s owns the pixels
+    [s p, min((s + 1) p, P)) of the (n, ho, wo) order; a split past P owns none and must hold zeros."""
+    P = N * Ho * Wo
+    nchunks = (P + 63) // 64
+    if L.oadg_conv2d_wgrad_variant(N, Ho, Wo, C, K, R, S_) == 256:
+        s0 = max(1, 256 // ((K // 256) * (C // 256) * R * S_))
+        rows = N * Ho
+        if R * S_ > 1 and Wo % 64 == 0 and rows >= s0:
+            per = -(-rows // s0)
+            assert splits == -(-rows // per), (splits, rows, per)
+            return per * Wo
+        assert splits == s0, (splits, s0)
+    return -(-nchunks // splits) * 64
+
+
+def wgrad_parts_exact(x, gy, R, S_, stride, pad, dil, splits, pix):
+    """(parts [splits][K][R*S][C] fp64, S [K][R*S][C]): the weight gradient over each split's pixel range
+    [s pix, (s + 1) pix) on its own, in the layout of the fp32 workspace, and the sum over |x| |gy| of all pixels"""
+    N, C, H, W = x.shape
+    K, Ho, Wo = gy.shape[1], gy.shape[2], gy.shape[3]
+    P = N * Ho * Wo
+    g = torch.zeros((splits * pix, K), dtype=torch.float64, device=x.device)
+    g[:P] = _nhwc64(gy).reshape(-1, K)[:splits * pix]
+    assert P <= splits * pix
+    g = g.view(splits, pix, K).transpose(1, 2)
+    parts = torch.zeros((splits, K, R * S_, C), dtype=torch.float64, device=x.device)
+    a = torch.zeros((K, R * S_, C), dtype=torch.float64, device=x.device)
+    for (i, j), v in _taps(_nhwc64(x), R, S_, stride, pad, dil, Ho, Wo):
+        m = torch.zeros((splits * pix, C), dtype=torch.float64, device=x.device)
+        m[:P] = v.reshape(-1, C)
+        m = m.view(splits, pix, C)
+        parts[:, :, i * S_ + j, :] = torch.bmm(g, m)
+        a[:, i * S_ + j, :] = torch.bmm(g.abs(), m.abs()).sum(0)
+    return parts, a
+
+
+def frozen_block_exact(x, ws, bs, downsample):
+    """csrc bottleneck_frozen.hip on integer operands, rounded as frozen_block_expect documents: (y fp64, [S of every
+    stage], first, live)"""
+    def stage(inp, w, b, pad):
+        r, S = conv_ref(inp, w, 1, pad, 1)
+        b64 = b.detach().to(torch.float64)
+        return r + b64, S + b64.abs()
+    r1, S1 = stage(x, ws[0], bs[0], 0)
+    t1 = bf16_rne(r1.clamp_min(0))
+    r2, S2 = stage(t1.permute(0, 3, 1, 2), ws[1], bs[1], 1)
+    t2 = bf16_rne(r2.clamp_min(0))
+    r3, S3 = stage(t2.permute(0, 3, 1, 2), ws[2], bs[2], 0)
+    Ss = [S1, S2, S3]
+    if downsample:
+        rd, Sd = stage(x, ws[3], bs[3], 0)
+        Ss.append(Sd)
+        s = bf16_rne(rd)
+    else:
+        s = _nhwc64(x)
+    t = bf16_rne(r3) + s
+    y = bf16_rne(t.clamp_min(0))
+    return y, Ss, (r1, r2, r3), y != 0
+
+
+def tile_width(M, K):
+    """output channels per workgroup of the 128-pixel tile family (variants 1 and 3): csrc conv_launch,
+    `const int tbn = (K % BN == 0 && m_tiles * (K / BN) > tbn64_max) ? BN : 64` with BN = 128, m_tiles = ceil(M / 128) and
+    tbn64_max = 256 - the 64-wide tile whenever 128-wide tiles would leave compute units without a workgroup"""
+    return 128 if (K % 128 == 0 and -(-M // 128) * (K // 128) > 256) else 64
+
+
 def frozen_block_expect(x, ws, bs, downsample):
     """csrc bottleneck_frozen.hip: y = relu(bf16(conv3(t2) + b3) + s), t2 = bf16(relu(conv2(t1) + b2)),
     t1 = bf16(relu(conv1(x) + b1)), s = x (identity block) or bf16(convd(x) + bd).  Errors of the rounded intermediates
@@ -277,6 +451,8 @@ class Auditor:
         self.bf16_handover = set()   # bank entries whose weight gradient reached the BN-fold chain rule in bf16
         self.narrow = None           # [dW, S, db, S_db] fp64 of the narrow RPN head's weight / bias over the step's calls
         self.kernels = set()         # the kernel instantiations whose launches were audited
+        self.last = None             # the instantiation of the latest audited launch
+        self.regime = None           # tests/test_conv_stress.py: the operand regime, kept apart in the table's rows
         self.failures = []
 
     # -- bookkeeping
@@ -289,6 +465,9 @@ class Auditor:
         rt, i = ratio(o, ref, b)
         if launched:
             self.kernels.add(kernel)
+            self.last = kernel
+        if self.regime is not None:
+            check = '[%s]' % self.regime if check is None else '[%s] %s' % (self.regime, check)
         kernel = kernel if check is None else '%s %s' % (kernel, check)
         row = self.table.setdefault(kernel, Row())
         row.calls += 1
@@ -299,6 +478,18 @@ class Auditor:
         if not rt <= 1.0:
             self.failures.append((kernel, tuple(shape), rt, row.where))
         return rt
+
+    def exact(self, kernel, shape, o, ref, check='exact integers'):
+        """``o`` must EQUAL ``ref`` (torch.equal: the integer-exact regime has one admissible output); booked as a row whose
+        bound, the absolute floor, makes any difference a failure"""
+        o64, r64 = o.detach().to(torch.float64), ref.detach().to(torch.float64)
+        same = o64.shape == r64.shape and torch.equal(o64, r64)
+        if o64.shape != r64.shape:
+            self.failures.append(('%s %s' % (kernel, check), tuple(shape), 'shape', (tuple(o64.shape), tuple(r64.shape))))
+            return False
+        rt = self.record(kernel, shape, o64, r64, torch.full_like(r64, ALPHA), check=check, launched=False)
+        assert same == (rt == 0.0), (kernel, check, same, rt)
+        return same
 
     def worst(self):
         return max((r.worst for r in self.table.values()), default=0.0)
@@ -347,6 +538,13 @@ class Auditor:
                 v = 3
             name = hip_conv.kernel_name(v, C, K, R, S_, stride, pad, residual is not None, mask is not None,
                                         mask_bits is not None, bits_out is not None)
+            if v in (1, 3):
+                # hip_conv.kernel_name knows the tile width by K % 128 only; conv_launch also takes the 64-wide tile on
+                # small maps (tile_width restates its rule): book the launch under the instantiation that ran
+                Ho = (H + 2 * pad - dil * (R - 1) - 1) // stride + 1
+                Wo = (W + 2 * pad - dil * (S_ - 1) - 1) // stride + 1
+                name = name.replace('conv_igemm_kernel<%d,' % (128 if K % 128 == 0 else 64),
+                                    'conv_igemm_kernel<%d,' % tile_width(N * Ho * Wo, K), 1)
             mb = mask_bits.clone() if mask_bits is not None else None
             del last_part[:]
             out = orig['conv_forward'](x, w, bias, residual, stride, pad, dil, relu, variant, mask, want_colsum, mask_bits,

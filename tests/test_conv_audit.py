@@ -229,8 +229,9 @@ _COMMON = {
     'prep_weights_multi_kernel',     # (the bank refresh after the audited step's optimizer step)
 }
 
-# the kernel instantiations each workload launches (spelt as hip_conv.kernel_name / rocprofv3 print them; the
-# weight-gradient kernel that reduces its own splits carries ' (+reduce)')
+# the kernel instantiations each workload launches (spelt as hip_conv.kernel_name / rocprofv3 print them, the tile width
+# of the 128-pixel family by conv_launch's rule - conv_audit.tile_width; the weight-gradient kernel that reduces its own
+# splits carries ' (+reduce)')
 EXPECTED = {
     'r50_fpn': {
         'bias_relu_maxpool_kernel',
@@ -245,6 +246,7 @@ EXPECTED = {
         'conv_igemm_kernel<128, false, 2, false>',
         'conv_igemm_kernel<128, true, 1, false>',
         'conv_igemm_kernel<128, true, 2, false>',
+        'conv_igemm_kernel<64, false, 2, false>',       # (P5 / P6: 128-wide tiles would leave compute units idle)
         'conv_igemm_s2_kernel<128, true>',
         'conv_pw_stream_kernel<128, true, false, true>',
         'conv_pw_stream_kernel<128, true, true, false>',
@@ -283,6 +285,11 @@ EXPECTED = {
         'conv_igemm_kernel<128, true, 1, false>',
         'conv_igemm_kernel<128, true, 1, true>',
         'conv_igemm_kernel<128, true, 2, false>',
+        'conv_igemm_kernel<64, false, 1, false>',       # (the 46 x 80 maps: 115 pixel tiles x K / 128 <= 256 workgroups)
+        'conv_igemm_kernel<64, false, 1, true>',
+        'conv_igemm_kernel<64, false, 2, false>',
+        'conv_igemm_kernel<64, true, 1, true>',
+        'conv_igemm_kernel<64, true, 2, false>',
         'conv_igemm_s2_kernel<128, false>',
         'conv_igemm_s2_kernel<128, true>',
         'conv_pw_stream_kernel<512, true, false, true>',
@@ -311,6 +318,8 @@ EXPECTED = {
         'conv_igemm_kernel<128, true, 1, false>',
         'conv_igemm_kernel<128, true, 1, true>',
         'conv_igemm_kernel<128, true, 2, false>',
+        'conv_igemm_kernel<64, false, 2, false>',
+        'conv_igemm_kernel<64, true, 2, false>',
         'conv_igemm_s2_kernel<128, true>',
         'conv_pw_stream_kernel<128, true, false, true>',
         'conv_pw_stream_kernel<128, true, true, false>',

@@ -270,20 +270,25 @@ def test_linear_reference_rejects_an_unpermuted_weight():
 # instantiations listed there.  The proposal and NMS kernels run in every training step too (its RoI proposals), audited
 # here first.
 # No test-time convolution reaches F.conv2d: a 'F.conv2d (library) C->K RxS' row in the set fails the test.
+# (the tile width of conv_igemm_kernel by conv_launch's rule, conv_audit.tile_width: 64-wide tiles on the small maps;
+#  the two instantiations below run in every workload but the two-image R101-DC5 one)
+_EXCEPT_DC5_B2 = {'conv_igemm_kernel<128, false, 2, false>', 'conv_igemm_kernel<64, true, 1, true>'}
 _COMMON = {
     'F.linear (library GEMM)', 'bias_relu_maxpool_kernel', 'bottleneck_frozen_first_kernel',
     'bottleneck_frozen_kernel', 'conv_igemm_kernel<128, false, 1, false>', 'conv_igemm_kernel<128, false, 1, true>',
-    'conv_igemm_kernel<128, false, 2, false>', 'conv_igemm_kernel<128, true, 1, true>', 'fc_weight_permute_kernel',
+    'conv_igemm_kernel<128, true, 1, true>', 'conv_igemm_kernel<64, false, 1, false>',
+    'conv_igemm_kernel<64, false, 1, true>', 'conv_igemm_kernel<64, false, 2, false>', 'fc_weight_permute_kernel',
     'nms_mask_kernel', 'nms_scan_kernel<3, 2>', 'prep_weights_kernel', 'roi_align_fwd_rows_kernel<unsigned short>',
     'rpn_decode_kernel', 'rpn_gather_kernel', 'rpn_order_kernel', 'sel_count_kernel2', 'sel_refine_kernel<1>',
     'sel_refine_kernel<2>', 'sel_scatter_kernel', 'sel_score_kernel', 'sel_sort_kernel', 'stem_conv7x7s2_kernel',
 }
 EXPECTED = {
-    'r50_fpn': _COMMON | {'conv_igemm256_kernel<false, 2>', 'conv_pw_stream_kernel<256, true, false, false>',
-                          'conv_pw_stream_kernel<512, false, false, false>', 'conv_pw_stream_kernel<512, true, false, false>',
-                          'fpn_topdown_fwd_kernel'},
-    'r101_dc5_b1': set(_COMMON),
-    # (two images: M = N Ho Wo of the 512 -> 2048 conv3 layers of layer4 reaches the streaming kernel)
+    'r50_fpn': _COMMON | _EXCEPT_DC5_B2 | {'conv_igemm256_kernel<false, 2>', 'conv_pw_stream_kernel<256, true, false, false>',
+                                           'conv_pw_stream_kernel<512, false, false, false>',
+                                           'conv_pw_stream_kernel<512, true, false, false>', 'fpn_topdown_fwd_kernel'},
+    'r101_dc5_b1': _COMMON | _EXCEPT_DC5_B2,
+    # (two images: M = N Ho Wo of the 512 -> 2048 conv3 layers of layer4 reaches the streaming kernel, and no launch is
+    #  left on the two-stage 128-wide tile or on the 64-wide pointwise tile with a residual)
     'r101_dc5_b2': _COMMON | {'conv_pw_stream_kernel<512, true, false, false>'},
 }
 # the ragged 800 x 1600 augmentations take no instantiation the 1024 x 2048 ones do not
