@@ -14,6 +14,8 @@
 //      registers (lane l owns words l, l+64, ...), the within-chunk dependency chain runs on v_readlane of the
 //      chunk's diagonal block, the updates of the next two chunks are OR-reductions of prefetched words and the
 //      farther ones loads consumed a chunk later: no memory round trip on the chain (round 2: 370 -> ~100 us).
+// tests/test_select_stress.py launches both scan instantiations (<3, 2> and the wide <MAX_WORDS_PER_LANE, 1>, up to the
+// 32,768-row limit) on constructed suppression graphs, dirty workspaces and partial counts.
 #include "common.h"
 #include <type_traits>
 

@@ -15,7 +15,8 @@
 //                  NMS kernels (csrc/nms.hip) and the valid count.
 // oadg_rpn_gather  the kept proposals as fixed-size lists [I, P, 5] (rows past the kept count: zero boxes, score -1).
 // Integer / index work is exact; the float arithmetic repeats the tensor expressions of the torch path operation for
-// operation (tests/test_hip_proposals.py compares both bit for bit).
+// operation (tests/test_hip_proposals.py compares both bit for bit).  tests/test_select_stress.py drives every kernel here
+// on constructed inputs and at its limits: 48 rows, k = 16,384, eight levels, M = 19,199, non-trivial means / stds.
 #include "common.h"
 #include "../../include/oadg_hip.h"
 
