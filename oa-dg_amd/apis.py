@@ -676,11 +676,263 @@ def parse_optimizer_config(cfg):
     return dict(grad_clip=clip)
 
 
+def single_gpu_test(model, dataset, pipe, amp, samples_per_gpu, max_samples=None, indices=None):
+    """apis/test.py:15-70 ``single_gpu_test``: ``model(return_loss=False, rescale=True, **data)`` over the dataset through
+    the device test pipeline, ``samples_per_gpu`` images per forward pass; one ``list[np.ndarray [k, 5]]`` (per class) per
+    image.  ``indices``: the images to test, in this order (a rank's shard); default: the first ``max_samples`` (all).
+    Runs on the current stream, draws no random number and leaves the model's mode alone (the caller's ``model.eval()``)."""
+    if indices is None:
+        indices = range(len(dataset) if max_samples is None else min(len(dataset), max_samples))
+    indices = list(indices)
+    results = []
+    for i in range(0, len(indices), samples_per_gpu):
+        imgs, boxes, labels = dataset.batch(indices[i:i + samples_per_gpu])
+        data = pipe.test_batch(imgs)
+        with torch.no_grad(), torch.autocast('cuda', dtype=amp, enabled=amp is not None):
+            results.extend(model(return_loss=False, rescale=True, **data))
+    return results
+
+
+def shard_indices(n, rank, world):
+    """the images rank ``rank`` of ``world`` tests: rank, rank + world, ... (apis/test.py multi_gpu_test's sampler order)"""
+    return list(range(rank, n, world))
+
+
+def merge_sharded_results(parts, size):
+    """``collect_results_cpu``'s reordering (apis/test.py:126-169): per-rank lists over the indices r, r + world, ... back
+    into dataset order, cut to ``size``.  The reference pads every shard to the same length and zips; here a shard may be
+    one short (or empty) - its turn is skipped."""
+    ordered = []
+    for i in range(max((len(p) for p in parts), default=0)):
+        for p in parts:
+            if i < len(p):
+                ordered.append(p[i])
+    assert len(ordered) >= size, f'{len(ordered)} results gathered for {size} images'
+    return ordered[:size]
+
+
+def collect_results(part, size, group=None):
+    """rank 0: every rank's results in dataset order; other ranks: None.  ONE ``all_gather_object`` - also the only point
+    where the ranks of a sharded validation wait for each other (no per-batch collective: a rank with one image fewer
+    runs one forward pass fewer and waits here)."""
+    rank, world = get_dist_info()
+    if world == 1:
+        return merge_sharded_results([part], size)
+    parts = [None] * world
+    dist.all_gather_object(parts, part, group=group)
+    return merge_sharded_results(parts, size) if rank == 0 else None
+
+
+def parse_evaluation(cfg, no_validate=False):
+    """``evaluation = dict(interval=1, metric='bbox', ...)`` of a config (apis/train.py:163-190) -> the keyword arguments
+    of EvalHook, or None when the config has no such key or ``--no-validate`` is given.  Everything is checked HERE, before
+    any training work: ``by_epoch=False`` (IterBasedRunner), a ``rule`` / ``save_best`` of the wrong kind, a metric the
+    val dataset's ``evaluate`` does not compute and every forwarded keyword it does not implement are rejected by name."""
+    ev = cfg.get('evaluation', None)
+    if no_validate or ev is None:
+        return None
+    ev = dict(ev)
+    if not ev.pop('by_epoch', True):
+        raise NotImplementedError('evaluation.by_epoch=False (IterBasedRunner) is not built: validation runs at epoch '
+                                  'boundaries of the EpochBasedRunner')
+    interval, start = ev.pop('interval', 1), ev.pop('start', None)
+    if not isinstance(interval, int) or interval <= 0:
+        raise ValueError(f'evaluation.interval must be a positive integer, but got {interval!r}')
+    if start is not None and start < 0:
+        raise ValueError(f'evaluation.start must be >= 0 or None, but got {start!r}')
+    metric = ev.pop('metric', None)
+    save_best, rule = ev.pop('save_best', None), ev.pop('rule', None)
+    if save_best is not None and not isinstance(save_best, str):
+        raise TypeError(f"evaluation.save_best must be None, 'auto' or a key name, but got {save_best!r}")
+    if rule not in (None, 'greater', 'less'):
+        raise KeyError(f"evaluation.rule must be 'greater', 'less' or None, but got {rule!r}")
+    # (interval, start, metric, save_best, rule, by_epoch configure the hook; everything else goes to dataset.evaluate)
+    eval_kwargs = {k: v for k, v in ev.items() if v is not None}
+    val = cfg.get('data', {}).get('val', None)
+    if val is None:
+        raise KeyError('evaluation is configured but the config has no data.val (pass --no-validate to train without it)')
+    from .evaluation import check_evaluate_args
+    from .registry import DATASETS
+    if val.get('type') not in DATASETS:
+        raise NotImplementedError(f"data.val.type={val.get('type')!r} is not a dataset of this build")
+    cls = DATASETS.get(val.get('type'))
+    if metric is None:
+        metric = cls.EVAL_PROTOCOLS[0]['metrics'][0] if getattr(cls, 'EVAL_PROTOCOLS', None) else 'bbox'
+    metrics = list(metric) if isinstance(metric, (list, tuple)) else [metric]
+    check_evaluate_args(cls, metrics, eval_kwargs)
+    if save_best not in (None, 'auto') and rule is None:
+        EvalHook.infer_rule(save_best)          # (raises for a key neither list knows, as mmcv's _init_rule does)
+    return dict(interval=interval, start=start, metric=metric, save_best=save_best, rule=rule, eval_kwargs=eval_kwargs)
+
+
+class EvalHook:
+    """mmcv ``EvalHook`` / ``DistEvalHook`` (mmcv/runner/hooks/evaluation.py, mmdet/core/evaluation/eval_hooks.py) for the
+    epoch-based loop of tools/train.py and ``train_detector``: validate after the epochs ``should_evaluate`` names, print
+    one ``Epoch(val) [E][N] k: v, ...`` line, keep the best checkpoint.
+
+    The val dataset (``test_mode=True``, the synthetic source where its files are absent, a ``RandomState`` of its own:
+    seed 12345 as tools/test.py) and the val ``DevicePipeline`` are built ONCE, by the first validation's caller
+    (``build``), and reused.  More than one rank: rank r tests images r, r + world, ... and rank 0 gathers, evaluates,
+    logs and saves (``collect_results``).  ``broadcast_bn_buffer`` is not built because it has nothing to do: every
+    BatchNorm of the named configs runs on frozen statistics -
+        configs/_base_/faster_rcnn_r50_fpn.py         backbone=dict(..., norm_eval=True, ...)
+        configs/_base_/faster_rcnn_r50_caffe_dc5.py   backbone=dict(..., norm_eval=True, ...)
+    - so the buffers never diverge between ranks.
+
+    A validation pass leaves the training run as it found it (DESIGN.md section 4 has the list that was checked): the
+    model goes ``eval()`` -> back to its mode (ResNet.train re-applies norm_eval and the frozen stages),
+    ``log_vars_on_host`` is put back, the pass runs under ``no_grad`` on the CURRENT stream with its own dataset, pipeline
+    and staging slots, and draws from no random stream."""
+
+    greater_keys = ('mAP', 'AP', 'AR', 'acc')
+    less_keys = ('loss',)
+    DUMP_ENV = 'OADG_EVAL_DUMP'        # =1: rank 0 pickles each validation's result list to work_dir/val_results_epoch_E.pkl
+
+    def __init__(self, interval=1, start=None, metric='bbox', save_best=None, rule=None, eval_kwargs=None,
+                 work_dir=None, logger=print, test_fn=None):
+        self.interval, self.start, self.metric = int(interval), start, metric
+        self.save_best, self.rule = save_best, rule
+        self.eval_kwargs = dict(eval_kwargs or {})
+        self.work_dir, self.logger = work_dir, logger
+        self.key_indicator = None if save_best in (None, 'auto') else save_best
+        if self.key_indicator is not None and self.rule is None:
+            self.rule = self.infer_rule(self.key_indicator)
+        self.best_score, self.best_ckpt = None, None
+        self.initial_flag = True
+        self.dataset = self.pipe = None
+        self.samples_per_gpu, self.amp = 1, None
+        # test_fn(model) -> the result list of this rank's shard (tests script it); default: single_gpu_test on the shard
+        self.test_fn = test_fn
+        self.validations = 0
+        self.last_seconds = None        # dict(test=, evaluate=) of the latest validation (tools/train.py's trace line)
+
+    # ------------------------------------------------------------------ schedule (mmcv EvalHook._should_evaluate)
+    def should_evaluate(self, epoch):
+        """``epoch``: index of the epoch that has just been trained (mmcv's ``runner.epoch`` in after_train_epoch)"""
+        if self.start is None:
+            return (epoch + 1) % self.interval == 0
+        if epoch + 1 < self.start:
+            return False
+        return (epoch + 1 - self.start) % self.interval == 0
+
+    def before_train_epoch(self, epoch, model, state_fn=None):
+        """mmcv's before_train_epoch / initial_flag: ONCE, before the first epoch of this run - a run that starts (resumes)
+        at or past ``start`` validates what it starts from"""
+        if not self.initial_flag:
+            return None
+        self.initial_flag = False
+        if self.start is not None and epoch >= self.start:
+            return self.after_train_epoch(epoch, model, state_fn)
+        return None
+
+    def after_train_epoch(self, epoch, model, state_fn=None):
+        self.initial_flag = False
+        if not self.should_evaluate(epoch):
+            return None
+        return self.validate(epoch, model, state_fn)
+
+    # ------------------------------------------------------------------ the pass itself
+    def build(self, data_cfg, device, amp, default_samples_per_gpu=1):
+        """the val dataset and its pipeline, once (apis/train.py:163-177: ``samples_per_gpu`` of the val split, default 1)"""
+        from .datasets import build_dataset
+        from .pipelines import DevicePipeline
+        data_cfg = dict(data_cfg.to_dict() if hasattr(data_cfg, 'to_dict') else data_cfg)
+        self.samples_per_gpu = int(data_cfg.pop('samples_per_gpu', default_samples_per_gpu))
+        self.amp = amp
+        self.dataset = build_dataset(data_cfg, default_args=dict(seed=12345, device=device, test_mode=True),
+                                     synthetic_fallback=True)
+        self.pipe = DevicePipeline(data_cfg['pipeline'], dtype=amp or torch.float32)
+        return self
+
+    def run_test(self, model):
+        """this rank's shard through the model in eval mode; the model's mode and ``log_vars_on_host`` are put back"""
+        rank, world = get_dist_info()
+        training, on_host = model.training, getattr(model, 'log_vars_on_host', None)
+        model.eval()
+        try:
+            if self.test_fn is not None:
+                return self.test_fn(model)
+            return single_gpu_test(model, self.dataset, self.pipe, self.amp, self.samples_per_gpu,
+                                   indices=shard_indices(len(self.dataset), rank, world))
+        finally:
+            model.train(training)
+            if on_host is not None:
+                model.log_vars_on_host = on_host
+
+    def validate(self, epoch, model, state_fn=None):
+        """test, gather, evaluate, log, save the best: returns the evaluation dict on rank 0, None elsewhere"""
+        rank, _ = get_dist_info()
+        t0 = time.time()
+        results = collect_results(self.run_test(model), len(self.dataset))
+        t1 = time.time()
+        self.validations += 1
+        if rank != 0:
+            return None
+        if os.environ.get(self.DUMP_ENV) == '1' and self.work_dir:
+            import pickle
+            with open(os.path.join(self.work_dir, f'val_results_epoch_{epoch + 1}.pkl'), 'wb') as f:
+                pickle.dump(results, f)
+        ev = self.dataset.evaluate(results, metric=self.metric, logger=None, **self.eval_kwargs)
+        self.last_seconds = dict(test=t1 - t0, evaluate=time.time() - t1)
+        if self.logger is not None:
+            self.logger(f'Epoch(val) [{epoch + 1}][{len(self.dataset)}] ' + ', '.join(
+                f'{k}: {v:.4f}' if isinstance(v, float) else f'{k}: {v}' for k, v in ev.items()))
+        if self.save_best is not None and ev:
+            self._save_best(epoch, ev, state_fn)
+        return ev
+
+    # ------------------------------------------------------------------ save_best (mmcv EvalHook._init_rule / _save_ckpt)
+    @classmethod
+    def infer_rule(cls, key):
+        if key in cls.greater_keys or (key not in cls.less_keys and any(k in key for k in cls.greater_keys)):
+            return 'greater'
+        if key in cls.less_keys or any(k in key for k in cls.less_keys):
+            return 'less'
+        raise ValueError(f'Cannot infer the rule for key {key}, thus a specific rule must be specified.')
+
+    def hook_msgs(self):
+        """what a checkpoint's ``meta.hook_msgs`` records (None before the first best)"""
+        if self.best_score is None:
+            return None
+        return dict(best_score=self.best_score, best_ckpt=self.best_ckpt)
+
+    def restore(self, hook_msgs):
+        """``--resume-from``: the best score so far, so that a worse epoch of the resumed run does not replace it"""
+        if hook_msgs:
+            self.best_score, self.best_ckpt = hook_msgs.get('best_score'), hook_msgs.get('best_ckpt')
+
+    def _save_best(self, epoch, ev, state_fn):
+        if self.key_indicator is None:           # 'auto': the first key evaluate returned
+            self.key_indicator = next(iter(ev))
+            if self.rule is None:
+                self.rule = self.infer_rule(self.key_indicator)
+        if self.key_indicator not in ev:
+            raise KeyError(f"save_best='{self.key_indicator}' is not among the evaluated keys {list(ev)}")
+        score = ev[self.key_indicator]
+        best = self.best_score if self.best_score is not None else (-float('inf') if self.rule == 'greater' else float('inf'))
+        if not (score > best if self.rule == 'greater' else score < best):          # strict: a tie keeps the earlier epoch
+            return
+        if self.best_ckpt and os.path.isfile(self.best_ckpt):
+            os.remove(self.best_ckpt)
+        self.best_score = score
+        self.best_ckpt = None
+        if state_fn is not None and self.work_dir:          # (no work_dir: the score is tracked, no file is written)
+            self.best_ckpt = os.path.join(self.work_dir, f'best_{self.key_indicator}_epoch_{epoch + 1}.pth')
+            state = state_fn()
+            state.setdefault('meta', {})['hook_msgs'] = self.hook_msgs()
+            torch.save(state, self.best_ckpt)
+        if self.logger is not None:
+            self.logger((f'Now best checkpoint is saved as {os.path.basename(self.best_ckpt)}. ' if self.best_ckpt else '') +
+                        f'Best {self.key_indicator} is {score:0.4f} at {epoch + 1} epoch.')
+
+
 def train_detector(model, data_iter, cfg, distributed=False, max_iters=None, logger=print, amp_dtype=None,
-                   iters_per_epoch=None):
+                   iters_per_epoch=None, validate=True, work_dir=None):
     """apis/train.py:71-212 reduced to the hot loop: build optimizer + schedule, iterate, log every
     cfg.log_config.interval iterations.  ``iters_per_epoch`` (or ``len(data_iter)`` when it has one) drives the
-    epoch-based step decay of the LR schedule."""
+    epoch-based step decay of the LR schedule and, when the config has an ``evaluation`` key and ``validate`` holds, the
+    EvalHook (after every completed epoch; a run cut short inside an epoch by ``max_iters`` does not validate)."""
+    ev_args = parse_evaluation(cfg, no_validate=not validate)
     optimizer = build_optimizer(model, cfg.optimizer)
     sched = StepLrSchedule(optimizer, **cfg.get('lr_config', dict(policy='step', step=[1 << 30])))
     engine = TrainEngine(model, optimizer, distributed, amp_dtype,
@@ -689,14 +941,30 @@ def train_detector(model, data_iter, cfg, distributed=False, max_iters=None, log
     rank, _ = get_dist_info()
     if iters_per_epoch is None and hasattr(data_iter, '__len__'):
         iters_per_epoch = len(data_iter)
+    hook, done = None, 0
+    if ev_args is not None:
+        if not iters_per_epoch:
+            raise ValueError('evaluation is configured: train_detector needs iters_per_epoch (or a sized data_iter) to '
+                             'know where an epoch ends')
+        hook = EvalHook(work_dir=work_dir, logger=logger if rank == 0 else None, **ev_args)
+        hook.build(cfg.data.val, next(model.parameters()).device, amp_dtype)
+
+        def state_fn():
+            return dict(state_dict=model.state_dict(), optimizer=optimizer.state_dict(),
+                        meta=dict(iter=done, epoch=done // iters_per_epoch))
+        hook.before_train_epoch(0, model, state_fn)
     t0 = time.time()
     for it, data in enumerate(data_iter):
         if max_iters is not None and it >= max_iters:
             break
         sched.set(it // iters_per_epoch if iters_per_epoch else 0, it)
         out = engine.step(data)
+        done = it + 1
         if rank == 0 and (it + 1) % interval == 0:
             lv = {k: (float(v) if not isinstance(v, float) else v) for k, v in out['log_vars'].items()}
             logger(f'iter {it + 1} lr {optimizer.param_groups[0]["lr"]:.5f} '
                    f'{(time.time() - t0) / (it + 1):.3f}s/it ' + ' '.join(f'{k}: {v:.4f}' for k, v in lv.items()))
+        if hook is not None and done % iters_per_epoch == 0:
+            hook.after_train_epoch(it // iters_per_epoch, model, state_fn)
+    engine.eval_hook = hook
     return engine

@@ -22,7 +22,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from . import staging
+from . import evaluation, staging
 from .registry import DATASETS, build_from_cfg
 
 
@@ -140,6 +140,12 @@ class CocoDataset:
 
     def __len__(self):
         return len(self.data_infos)
+
+    EVAL_PROTOCOLS = (evaluation.COCO_EVAL,)
+
+    def evaluate(self, results, metric='bbox', logger=None, **eval_kwargs):
+        """coco.py:364-573 for 'bbox' (XMLDataset: voc.py:28-106 for 'mAP'): evaluation.dataset_evaluate"""
+        return evaluation.dataset_evaluate(self, results, metric=metric, logger=logger, **eval_kwargs)
 
     def get_ann_info(self, idx):
         img_id = self.data_infos[idx]['id']
@@ -322,6 +328,10 @@ class XMLDataset(CocoDataset):
     """xml_style.py:14-154: VOC-style ``ann_file`` (one image id per line), ``{img_prefix}/{ann_subdir}/{id}.xml``
     annotations and ``{img_subdir}/{id}.jpg`` images.  Each XML file is parsed once, here, instead of on every
     ``_filter_imgs`` / ``get_ann_info`` call (same results).  Decoding, rings, ``batch()`` and ``flag`` are CocoDataset's."""
+    EVAL_PROTOCOLS = (evaluation.VOC_EVAL,)
+
+    def evaluate(self, results, metric='mAP', logger=None, **eval_kwargs):
+        return evaluation.dataset_evaluate(self, results, metric=metric, logger=logger, **eval_kwargs)
 
     def __init__(self, min_size=None, img_subdir='JPEGImages', ann_subdir='Annotations', **kwargs):
         assert self.CLASSES or kwargs.get('classes', None), 'CLASSES in `XMLDataset` can not be None.'
@@ -400,8 +410,8 @@ class XMLDataset(CocoDataset):
 
 @DATASETS.register_module()
 class SdgodDataset(XMLDataset):
-    """sdgod.py:12-29: the Diverse-Weather (S-DGOD) classes; the year is inferred from ``img_prefix``.  (Its VOC-protocol
-    ``evaluate`` is not restated yet.)"""
+    """sdgod.py:12-29: the Diverse-Weather (S-DGOD) classes; the year is inferred from ``img_prefix``.  ``evaluate`` is
+    XMLDataset's: ``eval_map`` in area mode (the 11-point VOC07 protocol of sdgod.py:67-70 is not restated)."""
     CLASSES = ('bus', 'bike', 'car', 'motor', 'person', 'rider', 'truck')
 
     def __init__(self, **kwargs):

@@ -163,6 +163,156 @@ def dataset_gt_anns(dataset, indices=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------ VOC-style mAP
+def average_precision(recalls, precisions):
+    """mean_ap.py:13-56, mode='area'."""
+    mrec = np.concatenate([[0.0], recalls, [1.0]])
+    mpre = np.concatenate([[0.0], precisions, [0.0]])
+    for i in range(len(mpre) - 1, 0, -1):
+        mpre[i - 1] = max(mpre[i - 1], mpre[i])
+    ind = np.where(mrec[1:] != mrec[:-1])[0]
+    return float(np.sum((mrec[ind + 1] - mrec[ind]) * mpre[ind + 1]))
+
+
+def eval_map(results, annotations, num_classes, iou_thr=0.5):
+    """mean_ap.py:298-440 (tpfp_default, no ignore / difficult flags): per-class AP and their mean."""
+    from .core import bbox_overlaps_np
+    aps = []
+    for c in range(num_classes):
+        scores, tp, n_gt = [], [], 0
+        for res, (gtb, gtl) in zip(results, annotations):
+            dets, gts = res[c], gtb[gtl == c]
+            n_gt += len(gts)
+            if len(dets) == 0:
+                continue
+            order = np.argsort(-dets[:, 4])
+            flags = np.zeros(len(dets), dtype=np.float32)
+            if len(gts):
+                ious = bbox_overlaps_np(dets[:, :4], gts)
+                best, arg = ious.max(axis=1), ious.argmax(axis=1)
+                covered = np.zeros(len(gts), dtype=bool)
+                for i in order:
+                    if best[i] >= iou_thr and not covered[arg[i]]:
+                        covered[arg[i]] = True
+                        flags[i] = 1
+            scores.append(dets[:, 4])
+            tp.append(flags)
+        if n_gt == 0:
+            continue
+        if not scores:
+            aps.append(0.0)
+            continue
+        s, t = np.concatenate(scores), np.concatenate(tp)
+        o = np.argsort(-s)
+        ctp, cfp = np.cumsum(t[o]), np.cumsum(1 - t[o])
+        aps.append(average_precision(ctp / max(n_gt, 1e-12), ctp / np.maximum(ctp + cfp, 1e-12)))
+    return (float(np.mean(aps)) if aps else 0.0), aps
+
+
+def dataset_box_anns(dataset, indices=None):
+    """per image (boxes [n, 4], labels [n]): ``get_ann_info`` of a file dataset, ``boxes`` of the synthetic one"""
+    idx = range(len(dataset)) if indices is None else indices
+    anns = []
+    for i in idx:
+        if hasattr(dataset, 'get_ann_info'):
+            a_ = dataset.get_ann_info(i)
+            anns.append((a_['bboxes'], a_['labels']))
+        else:
+            anns.append(dataset.boxes(i))
+    return anns
+
+
+def evaluate(results, ds, metrics, num_classes, mmdet_style=False):
+    """{'bbox': {AP, AP50, ...}} (COCO style) and / or {'mAP': ...} (VOC style AP@0.5).  ``mmdet_style``: the numbers and
+    names of CocoDataset.evaluate (maxDets 100 / 300 / 1000, mAP at 1000 detections: mAP, mAP_50, ..., AR@100, ...) -
+    what tools/test.py prints, comparable with the reference's logs; False: COCOeval's defaults (1 / 10 / 100), which is
+    what the robustness benchmark aggregates (test_robustness.py coco_eval_with_return)."""
+    out = {}
+    idx = range(len(results))
+    if 'bbox' in metrics:
+        kw = dict(max_dets=MMDET_MAX_DETS, names=MMDET_METRICS) if mmdet_style else {}
+        out['bbox'] = coco_eval_bbox(dataset_gt_anns(ds, idx), results, num_classes, **kw)
+    if 'mAP' in metrics:
+        m, aps = eval_map(results, dataset_box_anns(ds, idx), num_classes)
+        out['mAP'] = dict(mAP=m, per_class=aps)
+    return out
+
+
+# ------------------------------------------------------------------------------------------ dataset.evaluate
+# What ``dataset.evaluate(results, metric=..., **eval_kwargs)`` of the reference takes per protocol, and what of it this
+# build computes.  A metric or keyword of the reference that is not built is rejected BY NAME (NotImplementedError), one the
+# reference does not know either is a KeyError / TypeError as there - nothing is dropped silently.
+COCO_EVAL = dict(metrics=('bbox',), absent=('segm', 'proposal', 'proposal_fast'),
+                 kwargs=('proposal_nums', 'metric_items'),
+                 absent_kwargs=('jsonfile_prefix', 'outfile_prefix', 'classwise', 'iou_thrs', 'picked_label'))
+VOC_EVAL = dict(metrics=('mAP',), absent=('recall',), kwargs=('proposal_nums', 'iou_thr'), absent_kwargs=('scale_ranges',))
+
+
+def check_evaluate_args(cls, metrics, eval_kwargs):
+    """the metrics and forwarded keywords of an ``evaluation`` config against what ``cls.evaluate`` computes: raises with
+    the offending name (and the dataset class), so that a run stops before any training work instead of after an epoch"""
+    protos = getattr(cls, 'EVAL_PROTOCOLS', None)
+    if not protos:
+        raise NotImplementedError(f'{cls.__name__} has no evaluate()')
+    for m in metrics:
+        if not any(m in p['metrics'] for p in protos):
+            if any(m in p['absent'] for p in protos):
+                raise NotImplementedError(f"metric '{m}' of {cls.__name__}.evaluate is not built "
+                                          f"(built: {[x for p in protos for x in p['metrics']]})")
+            raise KeyError(f'metric {m} is not supported by {cls.__name__}')
+    used = [p for p in protos if any(m in p['metrics'] for m in metrics)]
+    for k in eval_kwargs:
+        if not any(k in p['kwargs'] for p in used):
+            if any(k in p['absent_kwargs'] for p in used):
+                raise NotImplementedError(f"evaluation key '{k}' ({cls.__name__}.evaluate(..., {k}=...)) is not built "
+                                          f"(built: {sorted({x for p in used for x in p['kwargs']})})")
+            raise TypeError(f"{cls.__name__}.evaluate() got an unexpected keyword argument '{k}'")
+
+
+def _num_classes(ds):
+    return len(getattr(ds, 'CLASSES', None) or range(getattr(ds, 'num_classes', 8)))
+
+
+def dataset_evaluate(ds, results, metric='bbox', logger=None, **eval_kwargs):
+    """``CocoDataset.evaluate`` (mmdet/datasets/coco.py:364-573, which CityscapesDataset delegates 'bbox' to) and
+    ``VOCDataset`` / ``SdgodDataset.evaluate`` (voc.py:28-106, sdgod.py:29-106) on this module's evaluators: the flat
+    ordered dict the reference returns.
+
+    'bbox': ``bbox_mAP, bbox_mAP_50, bbox_mAP_75, bbox_mAP_s, bbox_mAP_m, bbox_mAP_l`` as floats of 3 decimals (or the
+    ``metric_items`` asked for) and ``bbox_mAP_copypaste`` - the mmdet-style numbers: maxDets = ``proposal_nums`` =
+    (100, 300, 1000), mAP at the last of them.  'mAP': ``AP50`` (``AP{100 * iou_thr}`` per threshold, 3 decimals) and ``mAP``
+    (their mean) from ``eval_map``.  ``logger`` is the reference's parameter: nothing is printed here, the caller (EvalHook,
+    tools/test.py) prints what it returns."""
+    metrics = list(metric) if isinstance(metric, (list, tuple)) else [metric]
+    check_evaluate_args(type(ds), metrics, eval_kwargs)
+    assert len(results) == len(ds), f'{len(results)} results for {len(ds)} images'
+    nc = _num_classes(ds)
+    out = {}          # (insertion-ordered)
+    for m in metrics:
+        if m == 'bbox':
+            nums = tuple(eval_kwargs.get('proposal_nums', MMDET_MAX_DETS))
+            items = eval_kwargs.get('metric_items', None)
+            items = ([items] if isinstance(items, str) else list(items)) if items is not None else MMDET_METRICS[:6]
+            for it in items:
+                if it not in MMDET_METRICS:
+                    raise KeyError(f'metric item {it} is not supported')
+            stats = coco_eval_bbox(dataset_gt_anns(ds), results, nc, max_dets=nums, names=MMDET_METRICS)
+            for it in items:
+                out[f'bbox_{it}'] = float(f'{stats[it]:.3f}')
+            out['bbox_mAP_copypaste'] = ' '.join(f'{stats[k]:.3f}' for k in MMDET_METRICS[:6])
+        else:
+            thr = eval_kwargs.get('iou_thr', 0.5)
+            thrs = [thr] if isinstance(thr, float) else list(thr)
+            anns = dataset_box_anns(ds)
+            means = []
+            for t in thrs:
+                mean_ap, _ = eval_map(results, anns, nc, iou_thr=t)
+                means.append(mean_ap)
+                out[f'AP{int(t * 100):02d}'] = round(mean_ap, 3)
+            out['mAP'] = sum(means) / len(means)
+    return out
+
+
 # ------------------------------------------------------------------------------------------ corruption benchmark
 CORRUPTION_SETS = {   # tools/analysis_tools/test_robustness.py:225-256
     'all': ['gaussian_noise', 'shot_noise', 'impulse_noise', 'defocus_blur', 'glass_blur', 'motion_blur', 'zoom_blur',

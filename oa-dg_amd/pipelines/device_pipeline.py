@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from .. import _lib, staging
+from .. import evaluation as _evaluation
 from .._lib import check, ptr, stream_ptr
 from ..registry import DATASETS, PIPELINES, build_from_cfg
 from .corrupt import Corrupt
@@ -460,6 +461,13 @@ class SyntheticCityscapes:
 
     def __len__(self):
         return self.length
+
+    # stands in for a COCO-style dataset or (labels of a 7-class DWD config) a VOC-style one: both protocols
+    EVAL_PROTOCOLS = (_evaluation.COCO_EVAL, _evaluation.VOC_EVAL)
+
+    def evaluate(self, results, metric='bbox', logger=None, **eval_kwargs):
+        """CocoDataset.evaluate on the synthetic boxes (evaluation.dataset_evaluate)"""
+        return _evaluation.dataset_evaluate(self, results, metric=metric, logger=logger, **eval_kwargs)
 
     def boxes(self, idx):
         rs = np.random.RandomState((self.seed * 1000003 + idx) & 0x7fffffff)

@@ -14,11 +14,11 @@ import pickle
 import sys
 import time
 
-import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from train import DictAction  # noqa: E402
+from oadg_amd.evaluation import average_precision, eval_map, evaluate  # noqa: E402,F401  (the metric functions live there)
 
 
 def parse_args():
@@ -38,51 +38,6 @@ def parse_args():
     a = p.parse_args()
     os.environ.setdefault('LOCAL_RANK', str(a.local_rank))
     return a
-
-
-def average_precision(recalls, precisions):
-    """mean_ap.py:13-56, mode='area'."""
-    mrec = np.concatenate([[0.0], recalls, [1.0]])
-    mpre = np.concatenate([[0.0], precisions, [0.0]])
-    for i in range(len(mpre) - 1, 0, -1):
-        mpre[i - 1] = max(mpre[i - 1], mpre[i])
-    ind = np.where(mrec[1:] != mrec[:-1])[0]
-    return float(np.sum((mrec[ind + 1] - mrec[ind]) * mpre[ind + 1]))
-
-
-def eval_map(results, annotations, num_classes, iou_thr=0.5):
-    """mean_ap.py:298-440 (tpfp_default, no ignore / difficult flags): per-class AP and their mean."""
-    from oadg_amd.core import bbox_overlaps_np
-    aps = []
-    for c in range(num_classes):
-        scores, tp, n_gt = [], [], 0
-        for res, (gtb, gtl) in zip(results, annotations):
-            dets, gts = res[c], gtb[gtl == c]
-            n_gt += len(gts)
-            if len(dets) == 0:
-                continue
-            order = np.argsort(-dets[:, 4])
-            flags = np.zeros(len(dets), dtype=np.float32)
-            if len(gts):
-                ious = bbox_overlaps_np(dets[:, :4], gts)
-                best, arg = ious.max(axis=1), ious.argmax(axis=1)
-                covered = np.zeros(len(gts), dtype=bool)
-                for i in order:
-                    if best[i] >= iou_thr and not covered[arg[i]]:
-                        covered[arg[i]] = True
-                        flags[i] = 1
-            scores.append(dets[:, 4])
-            tp.append(flags)
-        if n_gt == 0:
-            continue
-        if not scores:
-            aps.append(0.0)
-            continue
-        s, t = np.concatenate(scores), np.concatenate(tp)
-        o = np.argsort(-s)
-        ctp, cfp = np.cumsum(t[o]), np.cumsum(1 - t[o])
-        aps.append(average_precision(ctp / max(n_gt, 1e-12), ctp / np.maximum(ctp + cfp, 1e-12)))
-    return (float(np.mean(aps)) if aps else 0.0), aps
 
 
 def build_model(cfg, checkpoint, dev, amp, allow_partial=False):
@@ -110,43 +65,15 @@ def build_model(cfg, checkpoint, dev, amp, allow_partial=False):
 
 def run_test(model, data_cfg, dev, amp, samples_per_gpu=1, max_samples=None):
     """single_gpu_test (apis/test.py:15-70) over one test-split config: (results, dataset, seconds)"""
+    from oadg_amd.apis import single_gpu_test
     from oadg_amd.datasets import build_dataset
     from oadg_amd.pipelines import DevicePipeline
     ds = build_dataset(data_cfg, default_args=dict(seed=12345, device=dev, test_mode=True), synthetic_fallback=True)
     pipe = DevicePipeline(data_cfg['pipeline'], dtype=amp or torch.float32)
-    n = len(ds) if max_samples is None else min(len(ds), max_samples)
-    results, t0 = [], time.time()
-    for i in range(0, n, samples_per_gpu):
-        imgs, boxes, labels = ds.batch(list(range(i, min(i + samples_per_gpu, n))))
-        data = pipe.test_batch(imgs)
-        with torch.no_grad(), torch.autocast('cuda', dtype=amp, enabled=amp is not None):
-            results.extend(model(return_loss=False, rescale=True, **data))
+    t0 = time.time()
+    results = single_gpu_test(model, ds, pipe, amp, samples_per_gpu, max_samples)
     torch.cuda.synchronize()
     return results, ds, time.time() - t0
-
-
-def evaluate(results, ds, metrics, num_classes, mmdet_style=False):
-    """{'bbox': {AP, AP50, ...}} (COCO style) and / or {'mAP': ...} (VOC style AP@0.5).  ``mmdet_style``: the numbers and
-    names of CocoDataset.evaluate (maxDets 100 / 300 / 1000, mAP at 1000 detections: mAP, mAP_50, ..., AR@100, ...) -
-    what tools/test.py prints, comparable with the reference's logs; False: COCOeval's defaults (1 / 10 / 100), which is
-    what the robustness benchmark aggregates (test_robustness.py coco_eval_with_return)."""
-    from oadg_amd import evaluation as E
-    out = {}
-    idx = range(len(results))
-    if 'bbox' in metrics:
-        kw = dict(max_dets=E.MMDET_MAX_DETS, names=E.MMDET_METRICS) if mmdet_style else {}
-        out['bbox'] = E.coco_eval_bbox(E.dataset_gt_anns(ds, idx), results, num_classes, **kw)
-    if 'mAP' in metrics:
-        anns = []
-        for i in idx:
-            if hasattr(ds, 'get_ann_info'):
-                a_ = ds.get_ann_info(i)
-                anns.append((a_['bboxes'], a_['labels']))
-            else:
-                anns.append(ds.boxes(i))
-        m, aps = eval_map(results, anns, num_classes)
-        out['mAP'] = dict(mAP=m, per_class=aps)
-    return out
 
 
 def main():

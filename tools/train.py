@@ -41,7 +41,8 @@ def parse_args():
     p.add_argument('--work-dir', help='the dir to save logs and models')
     p.add_argument('--resume-from', help='the checkpoint file to resume from')
     p.add_argument('--auto-resume', action='store_true', help='resume from the latest checkpoint automatically')
-    p.add_argument('--no-validate', action='store_true', help='accepted for compatibility (evaluation is out of scope)')
+    p.add_argument('--no-validate', action='store_true', help='whether not to evaluate the checkpoint during training (default: the config\'s `evaluation` key, '
+                        'when it has one, validates on data.val at its epoch interval)')
     g = p.add_mutually_exclusive_group()
     g.add_argument('--gpus', type=int, help='number of gpus to use (only applicable to non-distributed training)')
     g.add_argument('--gpu-ids', type=int, nargs='+', help='ids of gpus to use (non-distributed training)')
@@ -88,13 +89,14 @@ def main():
     a = parse_args()
     import oadg_amd
     from oadg_amd import Config, build_detector
-    from oadg_amd.apis import (TrainEngine, StepLrSchedule, build_optimizer, get_dist_info, init_dist,
-                               init_random_seed, parse_optimizer_config, set_random_seed)
+    from oadg_amd.apis import (EvalHook, TrainEngine, StepLrSchedule, build_optimizer, get_dist_info, init_dist,
+                               init_random_seed, parse_evaluation, parse_optimizer_config, set_random_seed)
     from oadg_amd.pipelines import DevicePipeline, SyntheticCityscapes
     cfg = Config.fromfile(a.config)
     if a.cfg_options:
         cfg.merge_from_dict(a.cfg_options)
     opt_hook = parse_optimizer_config(cfg)       # grad_clip honoured; fp16 / custom hooks rejected by name, before any work
+    ev_args = parse_evaluation(cfg, a.no_validate)   # None: no `evaluation` key or --no-validate; unknown keys rejected by name
     work_dir = a.work_dir or cfg.get('work_dir') or os.path.join('./work_dirs',
                                                                  os.path.splitext(os.path.basename(a.config))[0])
     distributed = a.launcher != 'none'
@@ -124,6 +126,7 @@ def main():
     model.log_vars_on_host = False
     resume = a.resume_from or (latest_checkpoint(work_dir) if a.auto_resume else None) or cfg.get('resume_from')
     start_iter = start_epoch = skip_batches = 0
+    resumed_hook_msgs = None
     optimizer = build_optimizer(model, cfg.optimizer)
     load_from = cfg.get('load_from')
     if resume:
@@ -137,6 +140,7 @@ def main():
         # a run stopped INSIDE an epoch (--max-iters) saved meta.epoch = the unfinished epoch and meta.inner_iter = the
         # batches of it already trained: that epoch is re-entered and those batches of its (seeded) order are skipped
         skip_batches = int(ck.get('meta', {}).get('inner_iter', 0))
+        resumed_hook_msgs = ck.get('meta', {}).get('hook_msgs')
         if rank == 0:
             print(f'resumed epoch {start_epoch}, iter {start_iter}' + (f' (+{skip_batches} batches into the epoch)'
                                                                         if skip_batches else '') + f' from {resume}', flush=True)
@@ -174,6 +178,21 @@ def main():
     interval = cfg.get('log_config', {}).get('interval', 50)
 
     ck_interval = int(cfg.get('checkpoint_config', {}).get('interval', 0) or 0)
+    # EvalHook (apis/train.py:163-190): the val dataset and its pipeline are built once, here; a resumed run takes the best
+    # score so far from the checkpoint's meta.hook_msgs
+    eval_hook = None
+    if ev_args is not None:
+        eval_hook = EvalHook(work_dir=work_dir, logger=(lambda m: print(m, flush=True)) if rank == 0 else None, **ev_args)
+        eval_hook.build(cfg.data.val, dev, amp)
+        eval_hook.restore(resumed_hook_msgs)
+
+    def make_state(epoch, it, inner=None):
+        meta = dict(iter=it, epoch=epoch, mmdet_version='2.20.0-compatible keys')
+        if inner is not None:
+            meta['inner_iter'] = inner
+        if eval_hook is not None and eval_hook.hook_msgs() is not None:
+            meta['hook_msgs'] = eval_hook.hook_msgs()        # (mmcv: runner.meta['hook_msgs'], restored by --resume-from)
+        return dict(state_dict=model.state_dict(), optimizer=optimizer.state_dict(), meta=meta)
 
     def save_checkpoint(epoch, it, inner=None):
         """CheckpointHook (by_epoch): epoch_{n}.pth after every ``interval``-th COMPLETED epoch (+ latest.pth).  ``inner``
@@ -184,12 +203,10 @@ def main():
         if inner is None:
             if (epoch + 1) % ck_interval != 0 and epoch + 1 != epochs:
                 return
-            state = dict(state_dict=model.state_dict(), optimizer=optimizer.state_dict(),
-                         meta=dict(iter=it, epoch=epoch + 1, mmdet_version='2.20.0-compatible keys'))
+            state = make_state(epoch + 1, it)
             torch.save(state, os.path.join(work_dir, f'epoch_{epoch + 1}.pth'))
         else:
-            state = dict(state_dict=model.state_dict(), optimizer=optimizer.state_dict(),
-                         meta=dict(iter=it, epoch=epoch, inner_iter=inner, mmdet_version='2.20.0-compatible keys'))
+            state = make_state(epoch, it, inner)
         torch.save(state, os.path.join(work_dir, 'latest.pth'))
 
     it, t0 = start_iter, time.time()
@@ -241,6 +258,8 @@ def main():
                 pending_load.append(loader.submit(load, nxt))
             staged.append((item[0], item[1], pipe.prefetch(*batch, worker_seed=wseed, ready=ready)))
     advance()
+    if eval_hook is not None:          # (a resumed run at or past evaluation.start validates what it starts from)
+        eval_hook.before_train_epoch(start_epoch, model, lambda: make_state(start_epoch, start_iter))
     last_epoch, done_in_epoch, cut_short = None, 0, False
     while staged:
         epoch, k, handle = staged.pop(0)
@@ -248,7 +267,18 @@ def main():
             cut_short = done_in_epoch < iters_per_epoch
             break
         if last_epoch is not None and epoch != last_epoch:
+            # mmcv's order at an epoch boundary: CheckpointHook (priority NORMAL) first, then EvalHook (LOW).  The next
+            # epoch's first batch is already being augmented on the pipeline's side stream: validation has its own
+            # dataset, pipeline and staging slots, and runs on this (the training) stream
             save_checkpoint(last_epoch, it)
+            if eval_hook is not None:
+                tv = time.time()
+                eval_hook.after_train_epoch(last_epoch, model, lambda: make_state(last_epoch + 1, it))
+                t_log += time.time() - tv        # 'time:' stays the iteration time (mmcv's IterTimerHook restarts per epoch)
+                if rank == 0 and eval_hook.last_seconds and os.environ.get('OADG_TRAIN_TRACE') == '1':
+                    print('  trace: validation ' + ', '.join(f'{k} {v:.2f} s' for k, v in eval_hook.last_seconds.items()),
+                          flush=True)
+                    eval_hook.last_seconds = None
         last_epoch = epoch
         sched.set(epoch, it)
         data = handle.get()
@@ -270,6 +300,8 @@ def main():
             t_log, it_log = now, it
     if last_epoch is not None:
         save_checkpoint(last_epoch, it, inner=done_in_epoch if cut_short else None)
+        if eval_hook is not None and not cut_short:          # (a run cut short inside an epoch does not validate)
+            eval_hook.after_train_epoch(last_epoch, model, lambda: make_state(last_epoch + 1, it))
     loader.shutdown(wait=False, cancel_futures=True)
 
 
