@@ -316,9 +316,33 @@ int oadg_oamix_normalize(const uint8_t* img, int H, int W, const float* mean_hos
  * PNG file -> uint8 [H][W][3] in B, G, R order at `out` (any host memory: the data set hands in a slice of a pinned
  * batch buffer) - zlib inflate + the five PNG row filters, one call without the interpreter lock.  8-bit grey / RGB / RGBA,
  * non-interlaced; OADG_EUNSUPPORTED for any other PNG variant (the caller decodes those with PIL), OADG_ESIZE when the
- * file's extent is not H x W, OADG_EIO when it cannot be read.  oadg_png_size: the extent from the header. */
+ * file's extent is not H x W, OADG_EIO when it cannot be read.  oadg_png_size: the extent from the header.
+ *   oadg_png_decode_gray16  mmcv.imread(inst_file, 'unchanged')  tools/dataset_converters/cityscapes.py:42
+ * 16-bit (or 8-bit, widened) greyscale, non-interlaced PNG -> native uint16 [H][W] at `out`; the same return codes. */
 int oadg_png_size(const char* path, int* height, int* width);
 int oadg_png_decode_bgr(const char* path, uint8_t* out, int H, int W);
+int oadg_png_decode_gray16(const char* path, uint16_t* out, int H, int W);
+
+/* ------------------------------------------------------------------------------------------------
+ * Instance-id maps -> per-instance statistics and run-length change points (csrc/instance_maps.hip)
+ *   replaces load_img_info  tools/dataset_converters/cityscapes.py:40-82 (np.unique, then per instance id
+ *            `inst_img == inst_id` -> pycocotools encode / area / toBbox: one pass over the map per instance)
+ * maps: uint16 [n][H][W], 2-byte aligned; H * W < 2^31 and W <= 4194240, n <= 65535 (OADG_EARG otherwise); ids below
+ * min_id (0..65535) are stuff.  Called from the offline converter tools/dataset_converters/cityscapes.py only.
+ *   oadg_instance_stats: for every id >= min_id present in map i, in ascending id order, the record
+ *     records[i][r] = {id, pixel count, xmin, ymin, xmax, ymax} (int32 [n][capacity][6]); counts[i] = the number of such ids.
+ *   oadg_instance_change_points: with f the map flattened COLUMN-major (p = x * H + y, the order of COCO RLE), for every
+ *     p >= 1 with f[p] != f[p-1] and max(f[p], f[p-1]) >= min_id, in ascending p, the triple
+ *     triples[i][r] = {p, f[p-1], f[p]} (int32 [n][capacity][3]); counts[i] = the number of such p.
+ * Both: counts[i] is the FULL number also when it exceeds capacity - then only the first `capacity` entries of map i were
+ * written and the caller calls again with more room; nothing is written past capacity.  Integer arithmetic and an ordered
+ * write (count, scan, write): the output bytes are the same from run to run.  The workspace (either call, same size) must
+ * hold oadg_instance_maps_workspace_bytes(n, H, W) bytes (0: a shape the calls refuse); OADG_ESIZE when it is smaller. */
+size_t oadg_instance_maps_workspace_bytes(int n, int H, int W);
+int oadg_instance_stats(const uint16_t* maps, int n, int H, int W, int min_id, int32_t* records, int capacity,
+                        int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+int oadg_instance_change_points(const uint16_t* maps, int n, int H, int W, int min_id, int32_t* triples, int capacity,
+                                int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * JPEG input files (csrc/jpeg_decode.hip): entropy stage on the HOST, pixel stage on the DEVICE

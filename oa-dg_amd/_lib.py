@@ -241,6 +241,10 @@ SIGNATURES = {
     'oadg_oamix_bbox_chain_multi': (ci, [vp, ci, vp]),
     'oadg_png_size': (ci, [c_char_p, POINTER(ci), POINTER(ci)]),
     'oadg_png_decode_bgr': (ci, [c_char_p, vp, ci, ci]),
+    'oadg_png_decode_gray16': (ci, [c_char_p, vp, ci, ci]),
+    'oadg_instance_maps_workspace_bytes': (cs, [ci, ci, ci]),
+    'oadg_instance_stats': (ci, [vp, ci, ci, ci, ci, vp, ci, vp, vp, cs, vp]),
+    'oadg_instance_change_points': (ci, [vp, ci, ci, ci, ci, vp, ci, vp, vp, cs, vp]),
     'oadg_jpeg_size': (ci, [c_char_p, POINTER(ci), POINTER(ci)]),
     'oadg_jpeg_coef_capacity': (cs, [ci, ci]),
     'oadg_jpeg_entropy_decode': (ci, [c_char_p, ci, ci, vp, cs, vp]),

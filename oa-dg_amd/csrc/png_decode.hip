@@ -7,7 +7,8 @@
 // interpreter lock back between them (and the caller then copies the image twice: np.asarray + the channel flip); here one
 // ctypes call (lock released for its whole duration) inflates the IDAT stream with zlib, undoes the five PNG row filters
 // and writes the pixels in OpenCV's channel order at their final place.  PNG is lossless: the bytes equal cv2's / PIL's.
-// Covers what such datasets hold: 8-bit grey / RGB / RGBA, non-interlaced; anything else returns OADG_EUNSUPPORTED and the
+// Covers what such datasets hold: 8-bit grey / RGB / RGBA, non-interlaced (oadg_png_decode_gray16: the 16-bit grey instance
+// maps of Cityscapes' gtFine, for tools/dataset_converters/cityscapes.py); anything else returns OADG_EUNSUPPORTED and the
 // caller falls back to PIL.  Host code only (compiled by hipcc with the rest of the library, links zlib).
 #include <stdio.h>
 #include <stdlib.h>
@@ -57,14 +58,17 @@ extern "C" int oadg_png_size(const char* path, int* height, int* width) {
     return OADG_OK;
 }
 
-extern "C" int oadg_png_decode_bgr(const char* path, uint8_t* out, int H, int W) {
-    if (!path || !out || H < 1 || W < 1) return OADG_EARG;
+namespace {
+
+// The whole file -> the inflated, still filtered scanlines of an H x W image: *raw holds h * (*line + 1) bytes (the caller
+// frees it), *bytes_pp the bytes per pixel.  `gray16`: accept grey of depth 8 or 16 only (else: 8-bit grey / RGB / RGBA).
+int inflate_file(const char* path, int H, int W, bool gray16, unsigned char** raw_out, long* line_out, int* bytes_pp) {
     FILE* f = fopen(path, "rb");
     if (!f) return OADG_EIO;
     fseek(f, 0, SEEK_END);
     const long size = ftell(f);
     fseek(f, 0, SEEK_SET);
-    if (size < 57) { fclose(f); return OADG_EUNSUPPORTED; }
+    if (size < 57) { fclose(f); return size < 0 ? OADG_EIO : OADG_EUNSUPPORTED; }
     unsigned char* file = (unsigned char*)malloc((size_t)size);
     if (!file) { fclose(f); return OADG_EIO; }
     const size_t got = fread(file, 1, (size_t)size, f);
@@ -77,9 +81,17 @@ extern "C" int oadg_png_decode_bgr(const char* path, uint8_t* out, int H, int W)
         const long w = be32(file + 16), h = be32(file + 20);
         const int depth = file[24], ctype = file[25], interlace = file[28];
         if (w != W || h != H) { rc = OADG_ESIZE; break; }
-        if (depth != 8 || interlace != 0 || !(ctype == 0 || ctype == 2 || ctype == 6)) break;
-        const int bpp = ctype == 0 ? 1 : (ctype == 2 ? 3 : 4);
+        if (interlace != 0) break;
+        int bpp;
+        if (gray16) {
+            if (ctype != 0 || !(depth == 8 || depth == 16)) break;
+            bpp = depth / 8;
+        } else {
+            if (depth != 8 || !(ctype == 0 || ctype == 2 || ctype == 6)) break;
+            bpp = ctype == 0 ? 1 : (ctype == 2 ? 3 : 4);
+        }
         const long line = w * bpp, need = h * (line + 1);
+        if (need > 0x7fffffffL) break;                     // (zlib's avail_out is 32 bits wide)
         raw = (unsigned char*)malloc((size_t)need);
         if (!raw) { rc = OADG_EIO; break; }
         z_stream zs;
@@ -106,25 +118,72 @@ extern "C" int oadg_png_decode_bgr(const char* path, uint8_t* out, int H, int W)
         const bool complete = (zrc == Z_STREAM_END || zrc == Z_OK) && zs.total_out == (uLong)need;
         inflateEnd(&zs);
         if (!complete) break;
-        // unfilter in place (a zero line above the first), then the pixels in B, G, R order
-        unsigned char* zero = (unsigned char*)calloc((size_t)line, 1);
-        if (!zero) { rc = OADG_EIO; break; }
-        const unsigned char* prev = zero;
-        bool ok = true;
-        for (long y = 0; y < h && ok; ++y) {
-            unsigned char* cur = raw + y * (line + 1) + 1;
-            const int ft = cur[-1];
-            if (ft > 4) { ok = false; break; }
-            unfilter(ft, cur, prev, line, bpp);
-            uint8_t* o = out + (size_t)y * W * 3;
-            if (bpp == 1) for (long x = 0; x < w; ++x) { o[3 * x] = o[3 * x + 1] = o[3 * x + 2] = cur[x]; }
-            else for (long x = 0; x < w; ++x) { o[3 * x] = cur[bpp * x + 2]; o[3 * x + 1] = cur[bpp * x + 1]; o[3 * x + 2] = cur[bpp * x]; }
-            prev = cur;
-        }
-        free(zero);
-        if (ok) rc = OADG_OK;
+        *raw_out = raw;
+        *line_out = line;
+        *bytes_pp = bpp;
+        raw = nullptr;
+        rc = OADG_OK;
     } while (false);
     free(raw);
     free(file);
+    return rc;
+}
+
+}  // namespace
+
+extern "C" int oadg_png_decode_bgr(const char* path, uint8_t* out, int H, int W) {
+    if (!path || !out || H < 1 || W < 1) return OADG_EARG;
+    unsigned char* raw = nullptr;
+    long line = 0;
+    int bpp = 0;
+    int rc = inflate_file(path, H, W, false, &raw, &line, &bpp);
+    if (rc != OADG_OK) return rc;
+    rc = OADG_EUNSUPPORTED;
+    // unfilter in place (a zero line above the first), then the pixels in B, G, R order
+    unsigned char* zero = (unsigned char*)calloc((size_t)line, 1);
+    if (!zero) { free(raw); return OADG_EIO; }
+    const unsigned char* prev = zero;
+    bool ok = true;
+    for (long y = 0; y < H && ok; ++y) {
+        unsigned char* cur = raw + y * (line + 1) + 1;
+        const int ft = cur[-1];
+        if (ft > 4) { ok = false; break; }
+        unfilter(ft, cur, prev, line, bpp);
+        uint8_t* o = out + (size_t)y * W * 3;
+        if (bpp == 1) for (long x = 0; x < W; ++x) { o[3 * x] = o[3 * x + 1] = o[3 * x + 2] = cur[x]; }
+        else for (long x = 0; x < W; ++x) { o[3 * x] = cur[bpp * x + 2]; o[3 * x + 1] = cur[bpp * x + 1]; o[3 * x + 2] = cur[bpp * x]; }
+        prev = cur;
+    }
+    free(zero);
+    if (ok) rc = OADG_OK;
+    free(raw);
+    return rc;
+}
+
+// 16-bit greyscale (Cityscapes *_gtFine_instanceIds.png): the same inflate and row filters (the filters work on BYTES, two to
+// a pixel), then the big-endian samples as native uint16 [H][W]; 8-bit grey is widened.
+extern "C" int oadg_png_decode_gray16(const char* path, uint16_t* out, int H, int W) {
+    if (!path || !out || H < 1 || W < 1) return OADG_EARG;
+    unsigned char* raw = nullptr;
+    long line = 0;
+    int bpp = 0;
+    int rc = inflate_file(path, H, W, true, &raw, &line, &bpp);
+    if (rc != OADG_OK) return rc;
+    unsigned char* zero = (unsigned char*)calloc((size_t)line, 1);
+    if (!zero) { free(raw); return OADG_EIO; }
+    const unsigned char* prev = zero;
+    rc = OADG_OK;
+    for (long y = 0; y < H; ++y) {
+        unsigned char* cur = raw + y * (line + 1) + 1;
+        const int ft = cur[-1];
+        if (ft > 4) { rc = OADG_EUNSUPPORTED; break; }
+        unfilter(ft, cur, prev, line, bpp);
+        uint16_t* o = out + (size_t)y * W;
+        if (bpp == 1) for (long x = 0; x < W; ++x) o[x] = cur[x];
+        else for (long x = 0; x < W; ++x) o[x] = (uint16_t)((cur[2 * x] << 8) | cur[2 * x + 1]);
+        prev = cur;
+    }
+    free(zero);
+    free(raw);
     return rc;
 }
