@@ -4,6 +4,7 @@ convolution implementation of :mod:`oadg_amd.layers`.
 Forward, data gradients (stride 1 and 2) and weight gradients run on the hand-written kernels; shapes they do not cover
 (C or K not a multiple of 64 / 128) fall back to ``aten.convolution_backward`` (MIOpen).
 """
+import collections
 import ctypes
 import os
 import weakref
@@ -25,33 +26,53 @@ TIMERS = None
 TIMERS_ONLY_VARIANT = None
 
 
-def _timed(family):
+def _t0(family):
+    """the recorded start event of a launch of kernel ``family`` when bench.py times that family, else None (the untimed
+    path: one global read and a comparison)"""
     if TIMERS is None:
-        return False
+        return None
     only = TIMERS_ONLY_VARIANT
-    return only is None or family == only or (isinstance(only, (set, frozenset, tuple, list)) and family in only)
-
-
-def _wgrad_events(x16, gy16, K, R, S):
-    """(family, kernel name) of a weight-gradient launch when it is to be timed, else None"""
-    if TIMERS is None:
+    if not (only is None or family == only or (isinstance(only, (set, frozenset, tuple, list)) and family in only)):
         return None
-    N, C = x16.shape[0], x16.shape[1]
-    v = _lib.lib().oadg_conv2d_wgrad_variant(N, gy16.shape[2], gy16.shape[3], C, K, R, S)
-    fam = 'wgrad256' if v == 256 else 'wgrad128'
-    if not _timed(fam):
-        return None
-    return 'conv_wgrad256_kernel' if v == 256 else 'conv_wgrad_kernel<%d>' % v
+    e0 = torch.cuda.Event(enable_timing=True)
+    e0.record()
+    return e0
 
 
-def _wgrad_record(name, e0, x16, gy16, K, R, S, stride, part_bytes):
+def _t1(e0, flops, nbytes, name, geo):
+    """the end of the launch ``_t0`` opened: one TIMERS entry"""
     e1 = torch.cuda.Event(enable_timing=True)
     e1.record()
+    TIMERS.append((e0, e1, flops, nbytes, name, geo))
+
+
+def _wgrad_cost(x16, gy16, K, R, S):
+    """(FLOP, algorithmic bytes) of a weight gradient: x and dy read once, dW (fp32) written once; the split partials are
+    implementation traffic"""
     N, C, H, W = x16.shape
+    P = N * gy16.shape[2] * gy16.shape[3]
+    return 2.0 * P * K * C * R * S, 2.0 * (N * H * W * C + P * K) + 4.0 * K * C * R * S
+
+
+def _wgrad_begin(x16, gy16, K, R, S):
+    """what the single-layer weight-gradient launches start with: (workspace bytes, workspace, start event or None,
+    kernel name when timed)"""
+    L = _lib.lib()
+    N, C = x16.shape[0], x16.shape[1]
     Ho, Wo = gy16.shape[2], gy16.shape[3]
-    # algorithmic bytes: x and dy read once, dW (fp32) written once; the split partials are implementation traffic
-    TIMERS.append((e0, e1, 2.0 * N * Ho * Wo * K * C * R * S, 2.0 * (N * H * W * C + N * Ho * Wo * K) + 4.0 * K * C * R * S,
-                   name, (N, H, W, C, K, R, stride, False, False, 1)))
+    nbytes = L.oadg_conv2d_wgrad_workspace_bytes(N, Ho, Wo, C, K, R, S)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x16.device)
+    e0 = name = None
+    if TIMERS is not None:
+        v = L.oadg_conv2d_wgrad_variant(N, Ho, Wo, C, K, R, S)
+        e0 = _t0('wgrad256' if v == 256 else 'wgrad128')
+        name = 'conv_wgrad256_kernel' if v == 256 else 'conv_wgrad_kernel<%d>' % v
+    return nbytes, ws, e0, name
+
+
+def _wgrad_end(e0, name, x16, gy16, K, R, S, stride):
+    N, C, H, W = x16.shape
+    _t1(e0, *_wgrad_cost(x16, gy16, K, R, S), name, (N, H, W, C, K, R, stride, False, False, 1))
 
 
 def _zeros(device):
@@ -76,8 +97,9 @@ def supported(x, weight, stride, padding, dilation):
 # prepared weights are used exactly once this step (shared convolutions get their bias gradients SUMMED by autograd),
 # and _PrepWeights.backward leaves dgamma raw for the deferred launch to finish with the same expression.
 DEFER_COLSUM = False
+DEFER_WGRAD = False         # the same for the small layers' weight gradients ("deferred, grouped weight gradients" below)
 _PENDING = []
-_STEP = 0                   # training-step counter: a bank entry counts the forward uses of its parameters per step
+_STEP = 0                 # training-step counter: a bank entry counts the forward uses of its parameters per step
 
 
 def begin_step(defer):
@@ -111,22 +133,16 @@ def flush_deferred(final=False):
 def _close_shared_leftovers():
     """a shared weight some of whose expected uses never reached _PrepWeights.backward (a level without a gradient): the
     jobs that did arrive returned no gradient, so their sum is added to the parameter's gradient here"""
-    global _WQ_WORK
     for ent in list(_SHARED_OPEN):
-        jobs, ent.shared = ent.shared, []
-        if not jobs:
+        if not ent.shared:
             continue
         w = ent.src[0]
-        leader = jobs[0]
-        K, C, R, S = leader.geo[4], leader.geo[3], leader.geo[5], leader.geo[6]
+        R, S = ent.shared[0].R, ent.shared[0].S
         wd = w.detach()
         krsc = int(R * S > 1 and not wd.is_contiguous() and wd.is_contiguous(memory_format=torch.channels_last))
         dw = torch.empty_like(wd)
-        leader.prep = (None, wd, None, None, None, 0.0, krsc, dw, None)
-        leader.members = len(jobs)
-        for j in jobs:
-            _WQ.append(j)
-            _WQ_WORK += j.work
+        _enqueue_shared(ent, _Consumer(gbias=None, w=wd, scale=None, mean=None, var=None, eps=0.0, flags=krsc, dw=dw,
+                                       dgamma=None))
         flush_wgrads()
         # This runs AFTER the backward pass: AccumulateGrad and its hooks are bypassed.  With no gradient on the parameter
         # yet (the normal case: none of the arrived uses returned one) a data-parallel reducer still sees it - its bucket
@@ -202,14 +218,19 @@ def flush_colsums():
     tdev = _STAGE.upload(tab, dev)         # a few flushes per step at most (one per gradient bucket)
     check(_lib.lib().oadg_colsum_reduce_multi(ptr(tdev), len(pend), blocks, stream_ptr()), 'oadg_colsum_reduce_multi')
     for e in pend:
-        for prm, alias in e.targets:
-            # AccumulateGrad adopts a gradient it holds the last reference to - then .grad IS the vector just finished.
-            # Had it copied instead (a tensor hook, an extra reference), the copy was taken too early: refresh it.
-            g = prm.grad
-            if g is not None and g.data_ptr() != alias.data_ptr() and g.shape == alias.shape:
-                g.copy_(alias)
+        _refresh_copied_grads(e.targets)
         e.done, e.part, e.fix, e.targets = True, None, None, []
     return len(pend)
+
+
+def _refresh_copied_grads(targets):
+    """[(parameter, alias of the tensor a deferred launch has just filled)]: AccumulateGrad adopts a gradient it holds the
+    last reference to - then .grad IS that tensor.  Had it copied instead (a tensor hook, an extra reference), the copy was
+    taken before the launch: refresh it."""
+    for prm, alias in targets:
+        g = prm.grad
+        if g is not None and g.data_ptr() != alias.data_ptr() and g.shape == alias.shape:
+            g.copy_(alias)
 
 
 # ---- deferred, grouped weight gradients ---------------------------------------------------------------------------------
@@ -218,8 +239,7 @@ def flush_colsums():
 # inside TrainEngine's backward their launches are collected and issued in groups: one weight-gradient launch + one
 # launch of the partial-sum / BN-fold consumer per group.  dW / dgamma travel up the graph as tensors that the group's
 # launches fill later - the same arrangement, with the same aliasing rules, as the deferred column sums above.
-DEFER_WGRAD = False
-WGRAD_SMALL = int(os.environ.get('OADG_WGRAD_SMALL', 40000))        # weight tiles x K-tiles below which a layer is deferred
+WGRAD_SMALL =int(os.environ.get('OADG_WGRAD_SMALL', 40000))        # weight tiles x K-tiles below which a layer is deferred
 # ... and the sum at which a group is launched.  Round 5: 65536 -> 196608 - with lists of several rounds (the planner's dispatch
 # replay) a larger group packs better and pays fewer launch tails: 27.3 -> 27.0 ms per step (131072: 27.1, 262144: 27.5 - a
 # list of more than three rounds is not planned), R101-DC5 18.4 -> 18.0
@@ -242,31 +262,47 @@ def wgrad_work(N, Ho, Wo, C, K, R, S):
     return (K // 256) * (C // 256) * R * S * ((N * Ho * Wo + 63) // 64)
 
 
+# LDS limits of the two consumer kernels of csrc/conv_mfma.hip, in their own units:
+MULTI_CONSUMER_LDS_FLOATS = 36000       # oadg_prep_conv_weights_bwd_parts_multi: max_crs, one C * R * S row of floats
+PARTS_CONSUMER_LDS_BYTES = 12000        # oadg_prep_conv_weights_bwd_parts: the bytes of one C * R * S row (it keeps five)
+
+
+# the operands of one job of the consumer launch (BN-fold chain rule, layout change, sum over the splits): csrc
+# oadg_prep_bwd_job; ``dw`` / ``dgamma`` are aliases of the tensors that went up the graph
+_Consumer = collections.namedtuple('_Consumer', 'gbias w scale mean var eps flags dw dgamma')
+
+
 class _WgradJob:
-    """one deferred weight gradient: the operands (kept alive), its geometry and - once _PrepWeights.backward has run -
-    the consumer's operands and the aliases of the tensors that went up the graph"""
-    __slots__ = ('x', 'gy', 'geo', 'work', 'prep', 'targets', 'members')
+    """one deferred weight gradient.  Either its operands ``x`` / ``gy`` (kept alive; launched with the group), or - a
+    single-layer launch has run already - its split partials ``parts`` / ``splits``: then only the consumer waits for the
+    group's consumer launch.  ``consumer`` / ``targets``: set by _PrepWeights.backward; ``consumer`` stays None on a
+    member of a shared-weight set."""
+    __slots__ = ('x', 'gy', 'parts', 'splits', 'C', 'K', 'R', 'S', 'stride', 'pad', 'dil', 'work', 'consumer', 'targets',
+                 'members')
 
-    def __init__(self, x16, gy16, K, R, S, stride, pad, dil):
-        N, C, H, W = x16.shape
-        self.x, self.gy = x16, gy16
-        self.geo = (N, H, W, C, K, R, S, stride, pad, dil)
-        self.work = wgrad_work(N, gy16.shape[2], gy16.shape[3], C, K, R, S)
-        self.prep, self.targets = None, []
+    def __init__(self, C, K, R, S, x=None, gy=None, stride=1, pad=0, dil=1, parts=None, splits=0):
+        self.x, self.gy, self.parts, self.splits = x, gy, parts, int(splits)
+        self.C, self.K, self.R, self.S, self.stride, self.pad, self.dil = C, K, R, S, stride, pad, dil
+        self.work = wgrad_work(x.shape[0], gy.shape[2], gy.shape[3], C, K, R, S) if x is not None else 0
+        self.consumer, self.targets = None, []      # targets: (parameter, alias) - where dW / dgamma should end up as .grad
         self.members = 1            # > 1: the leader of a shared-weight set - the next members - 1 jobs of the queue are uses
-                                    # of the same weight whose partials its consumer sums with its own (prep None on them)
+                                    # of the same weight whose partials its consumer sums with its own
 
 
-class _PartsJob:
-    """a weight gradient whose split partials already exist (a single-layer launch): only its CONSUMER (BN-fold chain rule,
-    layout change, sum over the splits) waits for the group's consumer launch"""
-    __slots__ = ('x', 'gy', 'geo', 'work', 'prep', 'targets', 'parts', 'splits', 'members')
+def _enqueue(job):
+    global _WQ_WORK
+    _WQ.append(job)
+    _WQ_WORK += job.work
 
-    def __init__(self, parts, splits, K, C, R, S):
-        self.x = self.gy = None
-        self.geo = (0, 0, 0, C, K, R, S, 1, 0, 1)
-        self.work, self.parts, self.splits = 0, parts, int(splits)
-        self.prep, self.targets, self.members = None, [], 1
+
+def _enqueue_shared(ent, consumer):
+    """the jobs waiting on bank entry ``ent`` as one shared-weight set: the first leads with ``consumer``, all enter the
+    queue side by side"""
+    jobs, ent.shared = ent.shared, []
+    _SHARED_OPEN.discard(ent)
+    jobs[0].consumer, jobs[0].members = consumer, len(jobs)
+    for j in jobs:
+        _enqueue(j)
 
 
 _GROUP_TRACE = {} if os.environ.get('OADG_BENCH_DIAG_CONV') == '1' else None
@@ -295,82 +331,67 @@ def wgrad_multi(jobs, target_blocks=256):
         r['part'] = ws.data_ptr() + off
         parts.append((ws.data_ptr() + off, int(r['splits'])))
         off += sz
-    name = 'conv_wgrad256_multi_kernel' if (TIMERS is not None and _timed('wgrad256')) else None
-    if name and _GROUP_TRACE is not None:
-        key = tuple((int(r['N']), int(r['H']), int(r['W']), int(r['C']), int(r['K']), int(r['R']), int(r['splits'])) for r in tab)
-        if key not in _GROUP_TRACE:      # bench.py OADG_BENCH_DIAG_CONV: what each grouped launch is made of
-            _GROUP_TRACE[key] = int(total)
-    if name:
-        e0 = torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = _t0('wgrad256')
     tdev = _STAGE.upload(tab, dev)
     check(L.oadg_conv2d_wgrad_multi(ptr(tdev), len(jobs), int(total), xcd_first, ptr(_zeros(dev)), stream_ptr()),
           'oadg_conv2d_wgrad_multi')
-    if name:
-        e1 = torch.cuda.Event(enable_timing=True)
-        e1.record()
-        fl = by = 0.0
-        for x16, gy16, K, R, S, stride, pad, dil in jobs:
-            N, C, H, W = x16.shape
-            P = N * gy16.shape[2] * gy16.shape[3]
-            fl += 2.0 * P * K * C * R * S
-            by += 2.0 * (N * H * W * C + P * K) + 4.0 * K * C * R * S
-        TIMERS.append((e0, e1, fl, by, name, (len(jobs), 0, 0, 0, 0, 0, 0, False, False, 1)))
+    if e0 is not None:
+        costs = [_wgrad_cost(*j[:5]) for j in jobs]
+        _t1(e0, sum(c[0] for c in costs), sum(c[1] for c in costs), 'conv_wgrad256_multi_kernel',
+            (len(jobs), 0, 0, 0, 0, 0, 0, False, False, 1))
+        if _GROUP_TRACE is not None:
+            key = tuple((int(r['N']), int(r['H']), int(r['W']), int(r['C']), int(r['K']), int(r['R']), int(r['splits'])) for r in tab)
+            if key not in _GROUP_TRACE:      # bench.py OADG_BENCH_DIAG_CONV: what each grouped launch is made of
+                _GROUP_TRACE[key] = int(total)
     return ws, parts
 
 
 def flush_wgrads():
-    """launch the deferred weight gradients collected so far as ONE group (+ one launch of their consumer).
-    (Round 6 re-measured the second stream for groups that fill up during the backward pass - this time only for small maps,
-    R101-DC5's 4 x 46 x 80 pixels, where the data-gradient launches leave most of the chip idle: 18.21 / 18.15 ms per step
-    against 18.11 / 18.88 without; R50-FPN with every group there 26.84 against 26.82.  Not kept.)"""
+    """launch the deferred weight gradients collected so far as ONE group (+ one launch of their consumer), on the current
+    stream (a second stream for them was measured again in round 6 and not kept - HISTORY.md, the table of round 6;
+    R50-FPN with every group there: 26.84 against 26.82 ms per step)"""
     global _WQ, _WQ_WORK
     jobs, _WQ, _WQ_WORK = _WQ, [], 0
     if not jobs:
         return 0
     L = _lib.lib()
-    dev = next(j.prep[1].device for j in jobs if j.prep is not None)
-    launch = [j for j in jobs if j.x is not None]
-    ws, parts = wgrad_multi([(j.x, j.gy) + j.geo[4:] for j in launch]) if launch else (None, [])
+    dev = next(j.consumer.w.device for j in jobs if j.consumer is not None)
+    launch = [j for j in jobs if j.parts is None]
+    ws, parts = wgrad_multi([(j.x, j.gy, j.K, j.R, j.S, j.stride, j.pad, j.dil) for j in launch]) if launch else (None, [])
     parts = iter(parts)
-    parts = [next(parts) if j.x is not None else (j.parts.data_ptr(), j.splits) for j in jobs]
+    parts = [next(parts) if j.parts is None else (j.parts.data_ptr(), j.splits) for j in jobs]
     # consumer jobs: one per queue entry that has consumer operands; the leader of a shared-weight set takes the partials of
     # its members too (they follow it in the queue, hence in the workspace: one array of sum(splits) tiles)
     cons = []
     for i, j in enumerate(jobs):
-        if j.prep is None:
+        if j.consumer is None:
             continue
         pp, splits = parts[i]
-        for m in range(1, j.members):
-            assert jobs[i + m].prep is None and jobs[i + m].geo[3:7] == j.geo[3:7]
-            splits += parts[i + m][1]
+        for m_ in jobs[i + 1:i + j.members]:
+            assert m_.consumer is None and (m_.C, m_.K, m_.R, m_.S) == (j.C, j.K, j.R, j.S)
+        splits += sum(sp for _, sp in parts[i + 1:i + j.members])
         cons.append((j, pp, splits))
     tab = np.zeros(len(cons), dtype=_lib.PREP_BWD_JOB)
     first, max_crs = 0, 0
     p_ = lambda t: 0 if t is None else t.data_ptr()  # noqa: E731
     for r, (j, pp, splits) in zip(tab, cons):
-        gb, w, scale, mean, var, eps, flags, dw, dgamma = j.prep
-        K, C, R, S = j.geo[4], j.geo[3], j.geo[5], j.geo[6]
-        r['part'], r['gbias'], r['w'], r['scale'], r['mean'], r['var'] = pp, p_(gb), p_(w), p_(scale), p_(mean), p_(var)
-        r['dw'], r['dgamma'], r['eps'], r['splits'] = p_(dw), p_(dgamma), eps, splits
-        r['K'], r['C'], r['R'], r['S'], r['w_krsc'], r['first_block'] = K, C, R, S, flags, first
-        first += K
-        max_crs = max(max_crs, C * R * S)
+        c = j.consumer
+        r['part'], r['gbias'], r['w'], r['scale'], r['mean'], r['var'] = pp, p_(c.gbias), p_(c.w), p_(c.scale), p_(c.mean), p_(c.var)
+        r['dw'], r['dgamma'], r['eps'], r['splits'] = p_(c.dw), p_(c.dgamma), c.eps, splits
+        r['K'], r['C'], r['R'], r['S'], r['w_krsc'], r['first_block'] = j.K, j.C, j.R, j.S, c.flags, first
+        first += j.K
+        max_crs = max(max_crs, j.C * j.R * j.S)
     tdev = _STAGE.upload(tab, dev)
     check(L.oadg_prep_conv_weights_bwd_parts_multi(ptr(tdev), len(cons), first, max_crs, stream_ptr()),
           'oadg_prep_conv_weights_bwd_parts_multi')
     for j in jobs:
-        for prm, alias in j.targets:
-            # AccumulateGrad adopts a gradient it holds the last reference to - then .grad IS the tensor just filled; had
-            # it copied instead (a tensor hook, an extra reference), the copy was taken before the launch: refresh it
-            g = prm.grad
-            if g is not None and g.data_ptr() != alias.data_ptr() and g.shape == alias.shape:
-                g.copy_(alias)
-        j.x = j.gy = j.prep = None
+        _refresh_copied_grads(j.targets)
+        j.x = j.gy = j.parts = j.consumer = None
         j.targets = []
-        if isinstance(j, _PartsJob):
-            j.parts = None
     return len(jobs)
+
+
+TOPDOWN_FUSED = os.environ.get('OADG_TOPDOWN_FUSED', '1') == '1'
 
 
 def topdown_ok(x, K, top):
@@ -382,9 +403,6 @@ def topdown_ok(x, K, top):
     if tuple(top.shape) != (N, K, H // 2, W // 2) or H & 1 or W & 1 or H < 2 or W < 2 or N * H * W >= 1 << 31:
         return False
     return _lib.lib().oadg_conv2d_auto_variant(N, H, W, C, K, 1, 1, 1, 0, 1) == 4
-
-
-TOPDOWN_FUSED = os.environ.get('OADG_TOPDOWN_FUSED', '1') == '1'
 
 
 def conv_forward(x, w, bias, residual, stride, pad, dil, relu, variant=0, mask=None, want_colsum=False, mask_bits=None,
@@ -404,10 +422,7 @@ def conv_forward(x, w, bias, residual, stride, pad, dil, relu, variant=0, mask=N
     variant = int(variant) or L.oadg_conv2d_auto_variant(N, H, W, C, K, R, S, stride, pad, dil)
     if variant == 4 and (mask is not None or (mask_bits is not None and bits_out is not None)):
         variant = 3                                    # the streaming pointwise kernel takes mask BITS, or writes them
-    timed = _timed(int(variant))                       # bench.py: only the dominant kernel family carries events
-    if timed:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = _t0(int(variant))                             # bench.py: only the dominant kernel family carries events
     part = None
     if want_colsum:
         rows = L.oadg_conv2d_pixel_tiles(N, H, W, C, K, R, S, stride, pad, dil, int(variant))
@@ -416,16 +431,14 @@ def conv_forward(x, w, bias, residual, stride, pad, dil, relu, variant=0, mask=N
                                      H, W, C, K, R, S, stride, pad, dil, int(bool(relu)) | (2 if res_up else 0), int(variant), ptr(mask),
                                      ptr(part), ptr(mask_bits), ptr(bits_out), stream_ptr()),
           'oadg_conv2d_nhwc_bf16')
-    if timed:
-        e1.record()
-        v = variant
-        TIMERS.append((e0, e1, 2.0 * N * Ho * Wo * K * C * R * S,
-                       2.0 * (N * H * W * C + K * C * R * S +
-                              N * Ho * Wo * K * (1 + (residual is not None) * (0.25 if res_up else 1) + (mask is not None)) +
-                              N * Ho * Wo * K / 16.0 * ((mask_bits is not None) + (bits_out is not None))),
-                       kernel_name(v, C, K, R, S, stride, pad, residual is not None, mask is not None, mask_bits is not None,
-                                   bits_out is not None),
-                       (N, H, W, C, K, R, stride, residual is not None, mask is not None, dil)))
+    if e0 is not None:
+        _t1(e0, 2.0 * N * Ho * Wo * K * C * R * S,
+            2.0 * (N * H * W * C + K * C * R * S +
+                   N * Ho * Wo * K * (1 + (residual is not None) * (0.25 if res_up else 1) + (mask is not None)) +
+                   N * Ho * Wo * K / 16.0 * ((mask_bits is not None) + (bits_out is not None))),
+            kernel_name(variant, C, K, R, S, stride, pad, residual is not None, mask is not None, mask_bits is not None,
+                        bits_out is not None),
+            (N, H, W, C, K, R, stride, residual is not None, mask is not None, dil))
     if want_colsum:
         return y, _colsum(part, K)
     return y
@@ -474,10 +487,7 @@ def conv_dgrad_s2(gy, wt, xshape, R, mask=None, want_colsum=False, mask_bits=Non
             geo.append((ph, pw, th, tw, off, ha, wa, (N * ha * wa + 127) // 128))
     part = torch.empty((sum(g[-1] for g in geo), C), dtype=torch.float32, device=gy.device) if want_colsum else None
     row = 0
-    timed = _timed(3)
-    if timed:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = _t0(3)
     if S2_ONE_LAUNCH:
         # all classes in one launch (csrc conv_igemm_s2_kernel): dy from HBM once, one launch ramp
         check(L.oadg_conv2d_dgrad_s2_nhwc_bf16(ptr(gy), ptr(wt), ptr(accumulate), ptr(gx), ptr(_zeros(gy.device)), N, Ho, Wo, K, C,
@@ -493,19 +503,18 @@ def conv_dgrad_s2(gy, wt, xshape, R, mask=None, want_colsum=False, mask_bits=Non
                                               th, tw, 0, 1, 0, ha, wa, H, W, 2, 2, ph, pw, ptr(mask), pptr,
                                               ptr(mask_bits), stream_ptr()), 'oadg_conv2d_nhwc_bf16_scatter')
         row += tiles
-    if timed:
+    if e0 is not None:
         # the class launches of one stride-2 data gradient as ONE entry: 2 * (output pixels of the forward conv) * K * C
         # * R * S FLOP (no zero-inserted dy), dy + the class filters read, dx (+ residual / mask) touched once
-        e1.record()
         post = accumulate is not None or mask is not None or mask_bits is not None
-        TIMERS.append((e0, e1, 2.0 * N * Ho * Wo * K * C * R * R,
-                       2.0 * (N * Ho * Wo * K + K * C * R * R + N * H * W * C * (1 + (accumulate is not None) + (mask is not None)))
-                       + N * H * W * C / 8.0 * (mask_bits is not None),
-                       ('conv_igemm_s2_kernel<%d, %s>' % (128 if C % 128 == 0 else 64, 'true' if post else 'false')
-                        if S2_ONE_LAUNCH else
-                        kernel_name(3, K, C, 2, 2, 1, 0, accumulate is not None, mask is not None, mask_bits is not None, False,
-                                    scatter=True)) + ' x%d (stride-2 dgrad classes)' % len(geo),
-                       (N, Ho, Wo, K, C, R, 2, accumulate is not None, mask is not None, 1)))
+        _t1(e0, 2.0 * N * Ho * Wo * K * C * R * R,
+            2.0 * (N * Ho * Wo * K + K * C * R * R + N * H * W * C * (1 + (accumulate is not None) + (mask is not None)))
+            + N * H * W * C / 8.0 * (mask_bits is not None),
+            ('conv_igemm_s2_kernel<%d, %s>' % (128 if C % 128 == 0 else 64, 'true' if post else 'false')
+             if S2_ONE_LAUNCH else
+             kernel_name(3, K, C, 2, 2, 1, 0, accumulate is not None, mask is not None, mask_bits is not None, False,
+                         scatter=True)) + ' x%d (stride-2 dgrad classes)' % len(geo),
+            (N, Ho, Wo, K, C, R, 2, accumulate is not None, mask is not None, 1))
     if want_colsum:
         return gx, _colsum(part, C)
     return gx
@@ -513,43 +522,28 @@ def conv_dgrad_s2(gy, wt, xshape, R, mask=None, want_colsum=False, mask_bits=Non
 
 def conv_wgrad(x16, gy16, K, R, S, stride, pad, dil):
     """dW [K,C,R,S] (fp32, channels_last strides) of y = conv(x, W): csrc/conv_mfma.hip conv_wgrad_kernel."""
-    L = _lib.lib()
     N, C, H, W = x16.shape
-    Ho, Wo = gy16.shape[2], gy16.shape[3]
-    nbytes = L.oadg_conv2d_wgrad_workspace_bytes(N, Ho, Wo, C, K, R, S)
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x16.device)
     dw = torch.empty((K, R, S, C), dtype=torch.float32, device=x16.device)
-    name = _wgrad_events(x16, gy16, K, R, S)
-    if name:
-        e0 = torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(L.oadg_conv2d_wgrad_nhwc_bf16(ptr(x16), ptr(gy16), ptr(dw), ptr(_zeros(x16.device)), ptr(ws), nbytes, N,
-                                        H, W, C, K, R, S, stride, pad, dil, stream_ptr()),
+    nbytes, ws, e0, name = _wgrad_begin(x16, gy16, K, R, S)
+    check(_lib.lib().oadg_conv2d_wgrad_nhwc_bf16(ptr(x16), ptr(gy16), ptr(dw), ptr(_zeros(x16.device)), ptr(ws), nbytes, N,
+                                                 H, W, C, K, R, S, stride, pad, dil, stream_ptr()),
           'oadg_conv2d_wgrad_nhwc_bf16')
-    if name:
-        _wgrad_record(name + '+reduce', e0, x16, gy16, K, R, S, stride, nbytes)
+    if e0 is not None:
+        _wgrad_end(e0, name + '+reduce', x16, gy16, K, R, S, stride)
     return dw.permute(0, 3, 1, 2)
 
 
 def conv_wgrad_parts(x16, gy16, K, R, S, stride, pad, dil):
     """(workspace, splits): the weight gradient of y = conv(x, W) as fp32 split partials [splits][K][R*S][C]; summed
     (with the BN-fold chain rule) by _PrepWeights.backward through oadg_prep_conv_weights_bwd_parts."""
-    import ctypes
-    L = _lib.lib()
     N, C, H, W = x16.shape
-    Ho, Wo = gy16.shape[2], gy16.shape[3]
-    nbytes = L.oadg_conv2d_wgrad_workspace_bytes(N, Ho, Wo, C, K, R, S)
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x16.device)
     splits = ctypes.c_int(0)
-    name = _wgrad_events(x16, gy16, K, R, S)
-    if name:
-        e0 = torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(L.oadg_conv2d_wgrad_parts_nhwc_bf16(ptr(x16), ptr(gy16), ptr(_zeros(x16.device)), ptr(ws), nbytes, N, H, W,
-                                              C, K, R, S, stride, pad, dil, ctypes.byref(splits), stream_ptr()),
+    nbytes, ws, e0, name = _wgrad_begin(x16, gy16, K, R, S)
+    check(_lib.lib().oadg_conv2d_wgrad_parts_nhwc_bf16(ptr(x16), ptr(gy16), ptr(_zeros(x16.device)), ptr(ws), nbytes, N, H,
+                                                       W, C, K, R, S, stride, pad, dil, ctypes.byref(splits), stream_ptr()),
           'oadg_conv2d_wgrad_parts_nhwc_bf16')
-    if name:
-        _wgrad_record(name, e0, x16, gy16, K, R, S, stride, nbytes)
+    if e0 is not None:
+        _wgrad_end(e0, name, x16, gy16, K, R, S, stride)
     return ws, splits.value
 
 
@@ -576,12 +570,26 @@ def _dummy_grad(like):
     return z.expand(like.shape)
 
 
-def _hip_wgrad(K, C, R, P):
+def _hip_wgrad(K, C):
     """use the csrc weight-gradient kernels?  With the per-shape kernel / split choice of conv_mfma.hip they match or
     beat MIOpen's igemm_wrw on every layer with K and C multiples of 128 (tools/bench_conv.py --wgrad: 1.0-1.6x)."""
-    if USE_HIP_WGRAD == 'auto':
-        return K % 128 == 0 and C % 128 == 0
-    return bool(USE_HIP_WGRAD) and K % 128 == 0 and C % 128 == 0
+    return bool(USE_HIP_WGRAD) and K % 128 == 0 and C % 128 == 0        # ('auto' = wherever the kernels apply)
+
+
+def _group_sized(deferrable, x16, Ho, Wo, K, C, R, S):
+    """is this layer's weight gradient small enough to ride in a group (flush_wgrads)?  ONE rule for _Conv2dMFMA.forward,
+    which counts the jobs a shared weight will receive, and _Conv2dMFMA.backward, which creates them: if the two disagreed,
+    every use of the shared weight would end in _close_shared_leftovers."""
+    return deferrable and C * R * S <= MULTI_CONSUMER_LDS_FLOATS and x16.numel() < 2 ** 32 and _hip_wgrad(K, C) and \
+        0 < wgrad_work(x16.shape[0], Ho, Wo, C, K, R, S) < WGRAD_SMALL
+
+
+def _sole_use(ent, leaf, no_grad_yet=True):
+    """do the gradients of this weight preparation go, as they are, to AccumulateGrad (``leaf``) of parameters used ONCE in
+    this step (bank entry ``ent``) that hold no gradient yet?  Only then may they be filled in later: a shared
+    convolution's gradients, or a second micro-batch's, are summed as they arrive."""
+    return leaf and ent is not None and ent.step == _STEP and ent.count == 1 and \
+        (not no_grad_yet or all(t.grad is None for t in ent.src))
 
 
 def _nhwc_bf16(t):
@@ -612,7 +620,9 @@ def _wgrad_dest(ctx, w, K, has_bn):
     AccumulateGrad adopts them and the reducer packs nothing - else new tensors"""
     from . import hip_ops
     ent = ctx.entry
-    if hip_ops.GRAD_SINK is not None and ctx.leaf_inputs and ent is not None and ent.step == _STEP and ent.count == 1 and \
+    # (no_grad_yet=False: whether the parameters hold a gradient is not asked here - with it, a second micro-batch would
+    #  take other tensors than it does today)
+    if hip_ops.GRAD_SINK is not None and _sole_use(ent, ctx.leaf_inputs, no_grad_yet=False) and \
             ent.src[0].dtype == torch.float32 and ent.src[0].stride() == w.stride():
         dw = hip_ops.grad_dest(ent.src[0], w)
         dgamma = None
@@ -622,6 +632,19 @@ def _wgrad_dest(ctx, w, K, has_bn):
                 torch.empty((K,), dtype=torch.float32, device=w.device)
         return dw, dgamma
     return torch.empty_like(w), (torch.empty((K,), dtype=torch.float32, device=w.device) if has_bn else None)
+
+
+def _attach_consumer(job, ctx, gbias, w, scale, mean, var, eps, flags, has_bn, record_targets):
+    """give ``job`` its consumer operands, writing to the (dW, dgamma) tensors of _wgrad_dest, which are returned;
+    ``record_targets``: remember the parameters these tensors should end up on as .grad (flush_wgrads checks that)"""
+    dw, dgamma = _wgrad_dest(ctx, w, w.shape[0], has_bn)
+    c = job.consumer = _Consumer(gbias, w, scale, mean, var, eps, flags, dw.detach(),
+                                 dgamma.detach() if dgamma is not None else None)
+    if record_targets:
+        job.targets.append((ctx.entry.src[0], c.dw))
+        if dgamma is not None:
+            job.targets.append((ctx.entry.src[1], c.dgamma))
+    return dw, dgamma
 
 
 class _PrepWeights(torch.autograd.Function):
@@ -681,7 +704,6 @@ class _PrepWeights(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gwf, gbias, _gwt):
-        global _WQ_WORK
         w, scale, mean, var = ctx.saved_tensors
         eps, has_bn, has_bias_in, K, C, R, S, krsc = ctx.cfg
         L = _lib.lib()
@@ -689,15 +711,11 @@ class _PrepWeights(torch.autograd.Function):
         gb = gbias.float().contiguous() if (gbias is not None and gbias.numel()) else None
         pend = pending_colsum(gbias)
         ent = ctx.entry
-        if pend is not None and not (gb is gbias and ctx.leaf_inputs and ent is not None and ent.step == _STEP and
-                                     ent.count == 1 and all(t.grad is None for t in ent.src)):
-            # the vector can only wait when it goes, as it is, to AccumulateGrad of parameters used ONCE in this step that
-            # hold no gradient yet (a shared convolution's bias gradients, or a second micro-batch, are summed there as
-            # they arrive)
-            resolve_colsum(gbias)
+        if pend is not None and not (gb is gbias and _sole_use(ent, ctx.leaf_inputs)):
+            resolve_colsum(gbias)       # the vector cannot wait (_sole_use)
             pend = None
         gb_now = None if pend is not None else gb
-        raw = 2 if pend is not None else 0
+        flags = int(krsc) | (2 if pend is not None else 0)      # 2: dgamma is left raw for flush_colsums() to finish
         tok = ctx.wtoken
         parts = None
         if tok is not None and tok.parts is not None:
@@ -713,62 +731,38 @@ class _PrepWeights(torch.autograd.Function):
             # at the same stride - so ONE consumer job sums them as the splits of a single layer and returns the weight's
             # whole small-map gradient; the earlier uses return no gradient at all.  (The P2 use is a launch of its own,
             # its gradient is added by autograd as before.)
-            job = parts
-            ent.shared.append(job)
+            ent.shared.append(parts)
             if len(ent.shared) < ent.expect_jobs:
-                job.prep = None                      # a member: launched and consumed with the group's last job
-                _SHARED_OPEN.add(ent)
+                _SHARED_OPEN.add(ent)                # a member: launched and consumed with the group's last job
             else:
                 dw = torch.empty_like(w)
-                leader = ent.shared[0]
-                job.prep = None
-                leader.prep = (None, w, scale, mean, var, eps, int(krsc) | raw, dw.detach(), None)
-                leader.members = len(ent.shared)
-                for j_ in ent.shared:
-                    _WQ.append(j_)
-                    _WQ_WORK += j_.work
-                ent.shared = []
-                _SHARED_OPEN.discard(ent)
+                _enqueue_shared(ent, _Consumer(gbias=None, w=w, scale=scale, mean=mean, var=var, eps=eps, flags=flags,
+                                               dw=dw.detach(), dgamma=None))
                 flush_wgrads()       # now: autograd ADDS this gradient to the other uses' (it is read right away)
         elif gwf is not None and isinstance(parts, _WgradJob):
             # a small layer inside TrainEngine's backward: its weight gradient joins the current group
-            dw, dgamma = _wgrad_dest(ctx, w, K, has_bn)
-            job = parts
-            defer = ctx.leaf_inputs and ent is not None and ent.step == _STEP and ent.count == 1 and \
-                all(t.grad is None for t in ent.src) and DEFER_WGRAD
-            job.prep = (gb_now, w, scale, mean, var, eps, int(krsc) | raw, dw.detach(),
-                        dgamma.detach() if dgamma is not None else None)
-            if defer:
-                job.targets.append((ent.src[0], job.prep[7]))
-                if dgamma is not None:
-                    job.targets.append((ent.src[1], job.prep[8]))
-            _WQ.append(job)
-            _WQ_WORK += job.work
+            defer = _sole_use(ent, ctx.leaf_inputs) and DEFER_WGRAD
+            dw, dgamma = _attach_consumer(parts, ctx, gb_now, w, scale, mean, var, eps, flags, has_bn, record_targets=defer)
+            _enqueue(parts)
             if not defer or _WQ_WORK >= WGRAD_GROUP:
                 flush_wgrads()       # (not deferrable after all: the gradient is summed on arrival - run the group now)
-        elif gwf is not None and parts is not None and DEFER_WGRAD and C * R * S <= 36000 and ctx.leaf_inputs and \
-                ent is not None and ent.step == _STEP and ent.count == 1 and all(t.grad is None for t in ent.src):
+        elif gwf is not None and parts is not None and DEFER_WGRAD and C * R * S <= MULTI_CONSUMER_LDS_FLOATS and \
+                _sole_use(ent, ctx.leaf_inputs):
             # partials of a single-layer launch inside TrainEngine's backward: their consumer joins the group's (one launch
-            # for all of them instead of one per layer - 14 launches of 9 - 22 us per step)
-            dw, dgamma = _wgrad_dest(ctx, w, K, has_bn)
-            job = _PartsJob(parts[0], parts[1], K, C, R, S)
-            job.prep = (gb_now, w, scale, mean, var, eps, int(krsc) | raw, dw.detach(),
-                        dgamma.detach() if dgamma is not None else None)
-            job.targets.append((ent.src[0], job.prep[7]))
-            if dgamma is not None:
-                job.targets.append((ent.src[1], job.prep[8]))
-            _WQ.append(job)
+            # for all of them instead of one per layer - 14 launches of 9 - 22 us per step); it waits for that group's flush
+            job = _WgradJob(C, K, R, S, parts=parts[0], splits=parts[1])
+            dw, dgamma = _attach_consumer(job, ctx, gb_now, w, scale, mean, var, eps, flags, has_bn, record_targets=True)
+            _enqueue(job)
         elif gwf is not None and parts is not None:        # fp32 split partials straight from the wgrad kernel
             dw, dgamma = _wgrad_dest(ctx, w, K, has_bn)      # w's strides (channels_last parameters keep theirs)
             check(L.oadg_prep_conv_weights_bwd_parts(ptr(parts[0]), parts[1], ptr(gb_now), ptr(w), ptr(scale), ptr(mean),
-                                                     ptr(var), eps, K, C, R, S, ptr(dw), ptr(dgamma), int(krsc) | raw,
-                                                     stream_ptr()),
+                                                     ptr(var), eps, K, C, R, S, ptr(dw), ptr(dgamma), flags, stream_ptr()),
                   'oadg_prep_conv_weights_bwd_parts')
         elif gwf is not None:
             gwf = gwf.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
             dw, dgamma = _wgrad_dest(ctx, w, K, has_bn)
             check(L.oadg_prep_conv_weights_bwd(ptr(gwf), ptr(gb_now), ptr(w), ptr(scale), ptr(mean), ptr(var), eps, K, C,
-                                               R, S, ptr(dw), ptr(dgamma), int(krsc) | raw, stream_ptr()),
+                                               R, S, ptr(dw), ptr(dgamma), flags, stream_ptr()),
                   'oadg_prep_conv_weights_bwd')
         if pend is not None:
             src = ent.src
@@ -1006,13 +1000,10 @@ class _Conv2dMFMA(torch.autograd.Function):
             ent = ctx.wtoken.entry
             if ent is not None and DEFER_WGRAD and SHARED_GROUP:
                 # (a weight used by several convolutions of a step - the RPN convolution on every pyramid level: how many of
-                #  its uses will hand a deferred job to _PrepWeights.backward; the predicate of _Conv2dMFMA.backward)
-                K_, C_, R_, S_ = wf.shape
-                work = wgrad_work(y.shape[0], y.shape[2], y.shape[3], C_, K_, R_, S_)
+                #  its uses will hand a deferred job to _PrepWeights.backward)
                 if ent.expect_step != _STEP:
                     ent.expect_step, ent.expect_jobs, ent.shared = _STEP, 0, []
-                if ctx.wtoken.deferrable and 0 < work < WGRAD_SMALL and C_ * R_ * S_ <= 36000 and x16.numel() < 2 ** 32 and \
-                        _hip_wgrad(K_, C_, R_, y.shape[0] * y.shape[2] * y.shape[3]):
+                if _group_sized(ctx.wtoken.deferrable, x16, y.shape[2], y.shape[3], *wf.shape):
                     ent.expect_jobs += 1
         return y
 
@@ -1096,13 +1087,13 @@ class _Conv2dMFMA(torch.autograd.Function):
                 gx = conv_forward(gy, wt, None, None, 1, dil * (R - 1) - pad, dil, False)
             need_x = False
         gw = None
-        if need_w and x16.numel() < 2 ** 32 and _hip_wgrad(K, C, R, gy.shape[0] * gy.shape[2] * gy.shape[3]):
+        if need_w and x16.numel() < 2 ** 32 and _hip_wgrad(K, C):
             wtok = ctx.wtoken
-            work = wgrad_work(gy.shape[0], gy.shape[2], gy.shape[3], C, K, R, S) if DEFER_WGRAD else 0
-            if wtok is not None and wtok.uses == 1 and wtok.deferrable and 0 < work < WGRAD_SMALL and C * R * S <= 36000:
-                wtok.parts = _WgradJob(x16, gy, K, R, S, stride, pad, dil)     # launched with its group (flush_wgrads)
+            if wtok is not None and wtok.uses == 1 and DEFER_WGRAD and \
+                    _group_sized(wtok.deferrable, x16, gy.shape[2], gy.shape[3], K, C, R, S):
+                wtok.parts = _WgradJob(C, K, R, S, x16, gy, stride, pad, dil)  # launched with its group (flush_wgrads)
                 gw = _dummy_grad(wf)
-            elif wtok is not None and wtok.uses == 1 and C * R * S * 4 <= 12000:
+            elif wtok is not None and wtok.uses == 1 and C * R * S * 4 <= PARTS_CONSUMER_LDS_BYTES:
                 wtok.parts = conv_wgrad_parts(x16, gy, K, R, S, stride, pad, dil)
                 gw = _dummy_grad(wf)          # the real gradient rides on the token (fp32 partials)
             else:
@@ -1158,15 +1149,12 @@ def narrow_params(w_cat, b_cat):
 
 def _n16_launch(kind, M, C, extra_bytes, fn):
     """one launch of csrc/narrow_head.hip, with an event pair when bench.py times the kernel families"""
-    if TIMERS is None or not _timed('n16'):
-        return fn()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
+    e0 = _t0('n16')
     r = fn()
-    e1.record()
-    # algorithmic bytes: the C-channel map and the 16-channel map once each (+ the mask bits of the data gradient)
-    TIMERS.append((e0, e1, 2.0 * M * C * 16, M * (2.0 * C + 32.0) + extra_bytes, 'n16_%s_kernel<%d>' % (kind, C),
-                   (1, M, 1, C, 16, 1, 1, False, kind == 'dgrad')))
+    if e0 is not None:
+        # algorithmic bytes: the C-channel map and the 16-channel map once each (+ the mask bits of the data gradient)
+        _t1(e0, 2.0 * M * C * 16, M * (2.0 * C + 32.0) + extra_bytes, 'n16_%s_kernel<%d>' % (kind, C),
+            (1, M, 1, C, 16, 1, 1, False, kind == 'dgrad'))
     return r
 
 
@@ -1325,31 +1313,26 @@ def frozen_bottleneck(x, block):
     # (feature taps, quantisation observers) runs them one by one.  OADG_FUSED_FROZEN_BLOCK=0: never fused.
     if any(m._forward_hooks or m._forward_pre_hooks for m in convs + bns + [block.relu]):
         return None
-    prep = [prepared(c.weight, bn, None, 0, c) for c, bn in zip(convs, bns)]
+    folded = [prepared(c.weight, bn, None, 0, c) for c, bn in zip(convs, bns)]
     x16 = _nhwc_bf16(x)
     N, _, H, W = x16.shape
     y = torch.empty((N, 256, H, W), dtype=torch.bfloat16, device=x16.device, memory_format=torch.channels_last)
-    (w1, b1, _), (w2, b2, _), (w3, b3, _) = prep[:3]
+    (w1, b1, _), (w2, b2, _), (w3, b3, _) = folded[:3]
     L = _lib.lib()
-    timed = TIMERS is not None and _timed('frozen_block')
-    if timed:
-        e0 = torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = _t0('frozen_block')
     if ds is None:
         check(L.oadg_bottleneck_frozen_256(ptr(x16), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(w3), ptr(b3), ptr(y), N, H, W,
                                            stream_ptr()), 'oadg_bottleneck_frozen_256')
     else:
-        wd, bd, _ = prep[3]
+        wd, bd, _ = folded[3]
         check(L.oadg_bottleneck_frozen_first_64(ptr(x16), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(w3), ptr(b3), ptr(wd),
                                                 ptr(bd), ptr(y), N, H, W, stream_ptr()), 'oadg_bottleneck_frozen_first_64')
-    if timed:
-        e1 = torch.cuda.Event(enable_timing=True)
-        e1.record()
+    if e0 is not None:
         M = N * H * W
         # algorithmic work of the block: its convolutions without the halo recomputation; bytes: x read once, y written once
-        TIMERS.append((e0, e1, 2.0 * M * (cin * 64 + 64 * 64 * 9 + 64 * 256 + (64 * 256 if ds is not None else 0)),
-                       2.0 * M * (cin + 256), 'bottleneck_frozen_kernel' if ds is None else 'bottleneck_frozen_first_kernel',
-                       (N, H, W, cin, 256, 3, 1, ds is None, False)))
+        _t1(e0, 2.0 * M * (cin * 64 + 64 * 64 * 9 + 64 * 256 + (64 * 256 if ds is not None else 0)), 2.0 * M * (cin + 256),
+            'bottleneck_frozen_kernel' if ds is None else 'bottleneck_frozen_first_kernel',
+            (N, H, W, cin, 256, 3, 1, ds is None, False))
     return y
 
 

@@ -1018,6 +1018,46 @@ def test_deferred_grouped_weight_gradients_in_a_backward_pass(dev, monkeypatch):
         hip_conv.DEFER_COLSUM = hip_conv.DEFER_WGRAD = False
 
 
+def test_shared_weight_with_a_use_that_receives_no_gradient(dev):
+    """hip_conv._close_shared_leftovers: one convolution on three maps (weight-gradient work 9 x 12, 9 x 3 and 9 x 1 tiles:
+    all three uses are counted as jobs of one shared-weight set), the loss on the first two outputs only.  The third job
+    never arrives, so the two that did wait on the bank entry past the backward pass; end_backward() runs them as one
+    group and puts their sum on the weight.  Against the immediate form: the weight gradient to fp32 rounding (another
+    summation order), the bias gradient - reduced on arrival in both forms - bit for bit."""
+    from oadg_amd import hip_conv, layers
+    hip_conv.enable(True)
+    try:
+        torch.manual_seed(3)
+        conv = layers.Conv2d(256, 256, 3, padding=1).to(dev).to(memory_format=torch.channels_last)
+        g = torch.Generator(device=dev).manual_seed(4)
+        xs = [torch.randn(2, 256, h, w, device=dev, generator=g).contiguous(memory_format=torch.channels_last)
+              for h, w in ((16, 24), (8, 12), (4, 6))]
+        res = {}
+        for mode in ('immediate', 'deferred'):
+            conv.zero_grad(set_to_none=True)
+            hip_conv.begin_step(defer=mode == 'deferred')
+            try:
+                with torch.autocast('cuda', dtype=torch.bfloat16):
+                    ys = [conv(x) for x in xs]
+                loss = sum((y.float() ** 2).mean() for y in ys[:2])
+                loss.backward()
+                if mode == 'deferred':      # both uses wait for the third: no gradient on the weight yet
+                    assert len(hip_conv._SHARED_OPEN) == 1 and conv.weight.grad is None
+            finally:
+                hip_conv.end_backward()
+            assert not hip_conv._WQ and not hip_conv._PENDING and not hip_conv._SHARED_OPEN
+            torch.cuda.synchronize()
+            assert conv.weight.grad is not None and torch.isfinite(conv.weight.grad).all()
+            res[mode] = (conv.weight.grad.detach().float().clone(), conv.bias.grad.detach().clone())
+        (wa, ba), (wb, bb) = res['immediate'], res['deferred']
+        assert wa.abs().max().item() > 0
+        assert (wb - wa).abs().max().item() <= 2e-5 * wa.abs().max().item() + 1e-9
+        assert torch.equal(ba, bb)
+    finally:
+        hip_conv.enable(False)
+        hip_conv.DEFER_COLSUM = hip_conv.DEFER_WGRAD = False
+
+
 @pytest.mark.parametrize('C,M', [(256, 2 * 40 * 56), (256, 4 * 13 * 7 + 3), (128, 64 * 9 + 1), (256, 8 * 256 * 512 // 16)])
 def test_narrow_head_kernels_match_fp32(dev, C, M):
     """csrc/narrow_head.hip: the 16-output-channel 1x1 forward, data gradient (+ ReLU mask bits + column sums) and weight
