@@ -345,6 +345,32 @@ int oadg_instance_change_points(const uint16_t* maps, int n, int H, int W, int m
                                 int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * PNG output: a resident batch -> the zlib stream of every image, and the stream -> a file (csrc/png_encode.hip)
+ *   replaces save_data  tools/analysis_tools/get_corrupted_dataset.py:83-113 (PIL.Image.fromarray(img).save(path): PNG row
+ *            filtering and zlib deflate of every corrupted image on one host core)
+ * imgs: uint8 [n][H][W][3]; bgr = 1: stored B, G, R (as the loaders produce it), 0: R, G, B - the stream always holds R, G, B.
+ * (3W + 1) * H < 2^31, W <= 4194304, n <= 65535 (OADG_EARG otherwise).  filter_mode: -1 = per row the PNG filter type with
+ * the smallest sum of absolute signed values (libpng's heuristic, over all five types), 0 .. 4 = that type on every row.
+ * The filtered bytes are cut into oadg_png_encode_segments(H, W) independent deflate blocks of literals only (dynamic
+ * Huffman codes limited to 15 bits, or a stored block where that is not smaller), each closed on a byte boundary.
+ *   oadg_png_encode_rgb8: the complete zlib stream of image i - 2-byte header, blocks, big-endian Adler-32 of the filtered
+ *     scanlines - at streams + i * capacity, stream_bytes[i] = its length.  stream_bytes[i] is the FULL length also when it
+ *     exceeds capacity - then only the first `capacity` bytes of image i were written and the caller calls again with more
+ *     room; nothing is written past capacity.  oadg_png_encode_stream_capacity(H, W) is enough for ANY content: at most
+ *     L + L / 64 + 64 with L = (3W + 1) * H (0: a shape the call refuses).  The bytes are the same from run to run, and
+ *     those of image i do not depend on the rest of the batch.  The workspace (16-byte aligned) must hold
+ *     oadg_png_encode_workspace_bytes(n, H, W) bytes; OADG_ESIZE when it is smaller.
+ *   oadg_png_write_rgb8 (HOST function, no device work, takes no interpreter lock): signature, IHDR (8-bit, colour type 2,
+ *     non-interlaced), IDAT chunk(s) holding the stream, IEND, each with its CRC-32; OADG_EIO when the file cannot be written.
+ * Called from the offline tools (tools/analysis_tools/get_corrupted_dataset.py, tools/bench_png_encode.py) only. */
+size_t oadg_png_encode_stream_capacity(int H, int W);
+int oadg_png_encode_segments(int H, int W);
+size_t oadg_png_encode_workspace_bytes(int n, int H, int W);
+int oadg_png_encode_rgb8(const uint8_t* imgs, int n, int H, int W, int bgr, int filter_mode, uint8_t* streams,
+                         size_t capacity, int64_t* stream_bytes, void* workspace, size_t workspace_bytes, void* stream);
+int oadg_png_write_rgb8(const char* path, const uint8_t* zstream_host, size_t bytes, int H, int W);
+
+/* ------------------------------------------------------------------------------------------------
  * JPEG input files (csrc/jpeg_decode.hip): entropy stage on the HOST, pixel stage on the DEVICE
  *   every entry below: LoadImageFromFile  mmdet/datasets/pipelines/loading.py:18-98 (mmcv.imfrombytes -> cv2.imdecode: colour,
  *             BGR byte order; libjpeg-turbo's defaults: islow IDCT, fancy upsampling)

@@ -245,6 +245,11 @@ SIGNATURES = {
     'oadg_instance_maps_workspace_bytes': (cs, [ci, ci, ci]),
     'oadg_instance_stats': (ci, [vp, ci, ci, ci, ci, vp, ci, vp, vp, cs, vp]),
     'oadg_instance_change_points': (ci, [vp, ci, ci, ci, ci, vp, ci, vp, vp, cs, vp]),
+    'oadg_png_encode_stream_capacity': (cs, [ci, ci]),
+    'oadg_png_encode_segments': (ci, [ci, ci]),
+    'oadg_png_encode_workspace_bytes': (cs, [ci, ci, ci]),
+    'oadg_png_encode_rgb8': (ci, [vp, ci, ci, ci, ci, ci, vp, cs, vp, vp, cs, vp]),
+    'oadg_png_write_rgb8': (ci, [c_char_p, vp, cs, ci, ci]),
     'oadg_jpeg_size': (ci, [c_char_p, POINTER(ci), POINTER(ci)]),
     'oadg_jpeg_coef_capacity': (cs, [ci, ci]),
     'oadg_jpeg_entropy_decode': (ci, [c_char_p, ci, ci, vp, cs, vp]),
