@@ -170,11 +170,11 @@ class ResNet(nn.Module):
     def _stem(self, x):
         """maxpool(relu(bn1(conv1(x)))) (resnet.py:631-637).  Frozen stem on the MI355X in bf16: the library convolution
         without bias, then bias + ReLU + max-pool in one pass (csrc/eltwise.hip) - same bits as the unfused chain."""
-        from . import hip_conv, hip_ops, layers
+        from . import hip_ops, layers
         c, bn, mp = self.conv1, self.bn1, self.maxpool
         frozen = not (c.weight.requires_grad or bn.weight.requires_grad or bn.bias.requires_grad or x.requires_grad)
-        if hip_conv.ENABLED and x.is_cuda and frozen and not bn.training and layers.FOLD_EVAL_BN and c.bias is None and \
-                (x.dtype == torch.bfloat16 or torch.is_autocast_enabled()) and c.out_channels % 8 == 0 and \
+        if hip_conv.on_path(x) and frozen and not bn.training and layers.FOLD_EVAL_BN and c.bias is None and \
+                c.out_channels % 8 == 0 and \
                 (mp.kernel_size, mp.stride, mp.padding, mp.dilation, mp.ceil_mode) == (3, 2, 1, 1, False):
             w, b = layers.folded_frozen(c, bn)
             x = x.to(torch.bfloat16)

@@ -12,7 +12,7 @@ from torch.profiler import record_function as _rf
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import hip_ops, staging
+from . import hip_conv, hip_ops, staging
 from .core import anchor_inside_flags, images_to_levels, multi_apply, unmap
 from .core.bbox import sample_many, sample_many_begin
 from .core.post_processing import parse_nms_cfg
@@ -378,10 +378,8 @@ class RPNHead(AnchorHead):
 
     def forward_single(self, x):
         c = self.rpn_conv
-        from . import hip_conv
         n_cls, n_reg = self.rpn_cls.out_channels, self.rpn_reg.out_channels
-        if hip_conv.ENABLED and x.is_cuda and (x.dtype == torch.bfloat16 or torch.is_autocast_enabled()) and \
-                n_cls + n_reg <= 128 and self.feat_channels % 64 == 0 and torch.is_grad_enabled():
+        if hip_conv.on_path(x) and n_cls + n_reg <= 128 and self.feat_channels % 64 == 0 and torch.is_grad_enabled():
             # rpn_cls and rpn_reg (3 + 12 output channels, rpn_head.py:56-59) as ONE 1x1 convolution on the MFMA
             # kernel, output channels zero-padded to its 128-channel tile: one pass over the 256-channel feature map
             # instead of two library convolutions forward and four backward, and - through the GradToken - the ReLU
@@ -390,7 +388,7 @@ class RPNHead(AnchorHead):
             # (in_token: an FPN level whose gradient this convolution finishes - necks.FPN._fpn_conv)
             x = conv2d(x, c.weight, c.bias, c.stride, c.padding, c.dilation, relu=True, out_token=tok,
                        in_token=getattr(x, '_oadg_token', None), owner=c)
-            if getattr(x.grad_fn, 'name', lambda: '')().startswith('_Conv2dMFMA'):
+            if tok.produced(x):
                 if hip_conv.NARROW_HEAD and n_cls + n_reg <= 16 and self.feat_channels in (128, 256) and \
                         self.rpn_cls.bias is not None and self.rpn_reg.bias is not None:
                     # round 4: 16-channel-wide head maps (csrc/narrow_head.hip) instead of a 128-channel tile with 15 live
@@ -404,7 +402,7 @@ class RPNHead(AnchorHead):
                 return cls, reg
             return self.rpn_cls(x), self.rpn_reg(x)
         x = conv2d(x, c.weight, c.bias, c.stride, c.padding, c.dilation, relu=True)   # relu(rpn_conv(x))
-        if hip_conv.ENABLED and x.is_cuda and x.dtype == torch.bfloat16 and n_cls + n_reg <= 128 and \
+        if hip_conv.on_path(x) and x.dtype == torch.bfloat16 and n_cls + n_reg <= 128 and \
                 self.feat_channels % 64 == 0 and self.rpn_cls.bias is not None and self.rpn_reg.bias is not None:
             # test time: rpn_cls and rpn_reg as the one zero-padded 1x1 convolution of the training path above, on the
             # MFMA kernel - their 3 / 12 (15 / 60) output channels alone are not a shape it takes, and the library
@@ -435,7 +433,6 @@ class RPNHead(AnchorHead):
         c = getattr(self, '_narrow_cache', None)
         if c is not None:
             return c
-        from . import hip_conv
         w = torch.cat([self.rpn_cls.weight, self.rpn_reg.weight])
         b = torch.cat([self.rpn_cls.bias, self.rpn_reg.bias])
         c = (w, b) + hip_conv.narrow_params(w, b)
@@ -444,16 +441,13 @@ class RPNHead(AnchorHead):
         return c
 
     def _narrow_ok(self, x):
-        from . import hip_conv
         n = self.rpn_cls.out_channels + self.rpn_reg.out_channels
-        return hip_conv.NARROW_HEAD and hip_conv.ENABLED and x.is_cuda and n <= 16 and self.feat_channels in (128, 256) and \
-            (x.dtype == torch.bfloat16 or torch.is_autocast_enabled()) and torch.is_grad_enabled() and \
-            self.rpn_cls.bias is not None and self.rpn_reg.bias is not None
+        return hip_conv.NARROW_HEAD and hip_conv.on_path(x) and n <= 16 and self.feat_channels in (128, 256) and \
+            torch.is_grad_enabled() and self.rpn_cls.bias is not None and self.rpn_reg.bias is not None
 
     def _forward_narrow(self, feats):
         """all pyramid levels through the 16-channel head as ONE autograd node (hip_conv._NarrowHead): rpn_conv per level,
         then the shared rpn_cls + rpn_reg on every level whose rpn_conv ran on the MFMA kernels"""
-        from . import hip_conv
         c = self.rpn_conv
         n_cls, n_reg = self.rpn_cls.out_channels, self.rpn_reg.out_channels
         hs, toks = [], []
@@ -462,7 +456,7 @@ class RPNHead(AnchorHead):
             h = conv2d(x, c.weight, c.bias, c.stride, c.padding, c.dilation, relu=True, out_token=tok,
                        in_token=getattr(x, '_oadg_token', None), owner=c)
             hs.append(h)
-            toks.append(tok if getattr(h.grad_fn, 'name', lambda: '')().startswith('_Conv2dMFMA') else None)
+            toks.append(tok if tok.produced(h) else None)
         sel = [i for i, t in enumerate(toks) if t is not None]
         ys = dict(zip(sel, hip_conv.narrow_head_levels([hs[i] for i in sel], *self._narrow_head_params(),
                                                         tokens=[toks[i] for i in sel]))) if sel else {}

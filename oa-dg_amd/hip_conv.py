@@ -1,8 +1,10 @@
 """autograd wrapper of the MFMA implicit-GEMM convolution (csrc/conv_mfma.hip) and its registration as the
 convolution implementation of :mod:`oadg_amd.layers`.
 
-Forward, data gradients (stride 1 and 2) and weight gradients run on the hand-written kernels; shapes they do not cover
-(C or K not a multiple of 64 / 128) fall back to ``aten.convolution_backward`` (MIOpen).
+Forward (C and K multiples of 64, else None to :mod:`oadg_amd.layers`), data gradients (stride 1 and 2) and weight
+gradients run on the hand-written kernels.  ``_Conv2dMFMA.backward`` is four steps (``_incoming_grad``, ``_data_grad``,
+``_weight_grad``, ``_residual_grad``) around the ``GradToken`` hand-offs; ``aten.convolution_backward`` (MIOpen) remains
+for data gradients without a second weight copy (``_wt_useful`` 0) and weight gradients with C or K no multiple of 128.
 """
 import collections
 import ctypes
@@ -397,7 +399,7 @@ TOPDOWN_FUSED = os.environ.get('OADG_TOPDOWN_FUSED', '1') == '1'
 def topdown_ok(x, K, top):
     """may ``conv1x1(x) + nearest_upsample_2x(top)`` run as ONE launch (the FPN top-down add in the lateral convolution's
     epilogue: csrc ConvArgs.res_up)?  The streaming pointwise kernel, even map sizes, ``top`` exactly half the size."""
-    if not (ENABLED and TOPDOWN_FUSED and x.is_cuda and top.is_cuda and x.dim() == 4 and top.dtype == torch.bfloat16):
+    if not (on_path(x) and TOPDOWN_FUSED and top.is_cuda and x.dim() == 4 and top.dtype == torch.bfloat16):
         return False
     N, C, H, W = x.shape
     if tuple(top.shape) != (N, K, H // 2, W // 2) or H & 1 or W & 1 or H < 2 or W < 2 or N * H * W >= 1 << 31:
@@ -949,13 +951,64 @@ class GradToken:
     ``extra`` and returns no gradient; the finisher adds ``extra`` in ITS epilogue (with the mask and the column sums) and
     closes the token.  Autograd's accumulation passes over the activation (13 per step, 0.8 ms) disappear.  Any other
     order stays correct: a depositor that finds the token closed (or never armed) returns its gradient as usual, autograd
-    adds it, P then sees a tensor other than ``grad_ptr`` and masks / reduces itself."""
-    __slots__ = ('extra', 'colsum', 'grad_ptr', 'bits', 'armed', 'closed', 'masked')
+    adds it, P then masks / reduces itself.  Every field but ``bits`` (P's forward) is written by these methods only."""
+    __slots__ = ('extra', 'colsum', 'grad_ptr', 'bits', 'armed', 'closed', 'masked', 'adopted')
 
     def __init__(self, masked=True):
         self.extra = self.colsum = self.grad_ptr = self.bits = None
-        self.armed = self.closed = False
+        self.armed = self.closed = self.adopted = False
         self.masked = masked        # False: t = P(...) without a ReLU (an FPN output): sums and column sums only
+
+    def adopt(self):                    # P's forward (_Conv2dMFMA) received this token as its ``out_token``
+        self.adopted = True
+
+    def produced(self, t):
+        """will a _Conv2dMFMA.backward claim this token for ``t``, the output of the call it went into as ``out_token``?"""
+        return self.adopted and t.grad_fn is not None
+
+    def arm(self):                      # the finisher's forward: its data gradient will finish the tensor's gradient
+        self.armed = True
+
+    def take(self):                     # a depositing convolution: the sum so far, for its own epilogue; then leave()
+        extra, self.extra = self.extra, None
+        return extra
+
+    def leave(self, gx):
+        self.extra = gx if gx.dtype == torch.bfloat16 else gx.to(torch.bfloat16)
+
+    def close(self):                    # the finisher's backward, first thing, needed or not: what was left here
+        self.closed = True
+        return self.take()
+
+    def finish(self, gx, colsum):       # ... after the launch that masked gx: P may trust exactly this tensor
+        self.colsum, self.grad_ptr = colsum, gx.data_ptr()
+        return gx
+
+    def may_deposit(self):
+        """a depositor asks first.  One running AFTER the finisher taints the token, whatever DEPOSIT says: autograd adds
+        its returned gradient to the finisher's - possibly IN PLACE into the very tensor ``grad_ptr`` names (InputBuffer
+        does when it holds the last reference), which P's pointer check could not see: P masks the sum itself."""
+        if self.closed:
+            self.grad_ptr = self.colsum = None
+        return self.armed and not self.closed and DEPOSIT
+
+    def deposit(self, g):
+        """a gradient map computed elsewhere (RoIAlign): True = it stays here, False = the caller returns it"""
+        ok = self.may_deposit() and g.dtype == torch.bfloat16
+        if ok:
+            self.extra = g if self.extra is None else self.extra + g
+        return ok
+
+    def hand_off(self, gy):             # the identity path of the block C opens (``res_token``): unconditional
+        self.extra = gy
+
+    def claim(self, gy):
+        """P's backward -> (trusted, column sums): is ``gy`` the very tensor the finisher returned?  Clears the hand-off."""
+        ok = self.grad_ptr is not None and self.grad_ptr == gy.data_ptr() and gy.dtype == torch.bfloat16 and \
+            gy.is_contiguous(memory_format=torch.channels_last)
+        colsum = self.colsum if ok else None
+        self.grad_ptr = self.colsum = None
+        return ok, colsum
 
 
 RELU_BITS = True
@@ -968,18 +1021,94 @@ def y_numel(x, w, stride, pad, dil):
     return N * K * ((H + 2 * pad - dil * (R - 1) - 1) // stride + 1) * ((W + 2 * pad - dil * (S - 1) - 1) // stride + 1)
 
 
+def _incoming_grad(gy, y, out_token, wtoken, want_b):
+    """step 1 of _Conv2dMFMA.backward -> (dy bf16 NHWC through the ReLU mask, bias gradient or None, bias gradient still
+    wanted): claimed from the consumer's epilogue, or one pass of csrc/eltwise.hip, or torch where that does not apply"""
+    trusted, colsum = out_token.claim(gy) if out_token is not None else (False, None)
+    if trusted:
+        gb = colsum if want_b else None               # masked and reduced by the consumer's dgrad epilogue
+        if pending_colsum(gb) is not None and not (wtoken is not None and wtoken.uses == 1):
+            resolve_colsum(gb)          # shared / unknown weights: autograd may sum this vector with others right away
+        return gy, gb, False
+    if (y is not None or want_b) and gy.dtype in (torch.bfloat16, torch.float32) and gy.shape[1] % 8 == 0 and \
+            gy.is_contiguous(memory_format=torch.channels_last):
+        return (*relu_bias_bwd(gy, y, want_b), False)               # mask + cast + bias gradient: one pass over dy
+    gy = _nhwc_bf16(gy)
+    if y is not None:
+        gy = torch.ops.aten.threshold_backward(gy, y, 0)
+    return gy, None, want_b
+
+
+def _data_grad(gy, x16, wf, wt, stride, pad, dil, add, tok, deposit):
+    """step 2 -> (dx, what torch still has to add to it).  ``add``: a gradient of the same tensor (deposited / handed over),
+    summed in the launch's epilogue where the kernel takes one; ``tok``: the token to finish; ``deposit``: dx + add is
+    complete on return (maybe in ``add``).  Without ``wt``: the library's dx for a depositor, else None (backward's call)."""
+    R, kw = wf.shape[2], {}
+    fin = wt is not None and tok is not None and (stride == 1 or (add is None and tok.masked))
+    if fin:     # [* (x > 0): the producer's bits, else x itself], column sums -> the producer's bias gradient
+        mb = tok.bits if tok.masked else None
+        kw = dict(mask=x16 if (mb is None and tok.masked) else None, want_colsum=True, mask_bits=mb)
+    if wt is None:
+        if not deposit:
+            return None, add
+        gx = torch.ops.aten.convolution_backward(gy, x16, wf, None, [stride, stride], [pad, pad], [dil, dil], False,
+                                                 [0, 0], 1, [True, False, False])[0]
+    elif stride == 2 and deposit and R == 1 and add is not None:
+        return conv_dgrad_s2(gy, wt, x16.shape, R, accumulate=add), None      # in place, on its strided grid
+    elif stride == 2:   # Bottleneck.conv2 / downsample of a stage's first block: parity-class convolutions
+        gx = conv_dgrad_s2(gy, wt, x16.shape, R, **kw)
+    else:               # dx = conv(dy, rot180(W)^T) [+ add]
+        gx, add = conv_forward(gy, wt, None, add, 1, dil * (R - 1) - pad, dil, False, **kw), None
+    if fin:
+        gx = tok.finish(*gx)
+    if deposit and add is not None:
+        gx, add = gx + add.to(gx.dtype), None
+    return gx, add
+
+
+def _weight_grad(wtok, x16, wf, gy, stride, pad, dil):
+    """step 3 -> dW by the csrc kernels, in one of three forms (a job of the step's grouped launch, fp32 partials riding
+    on the weight token, the finished gradient), or None: the library's"""
+    K, C, R, S = wf.shape
+    if not (x16.numel() < 2 ** 32 and _hip_wgrad(K, C)):
+        return None
+    if wtok is not None and wtok.uses == 1 and DEFER_WGRAD and \
+            _group_sized(wtok.deferrable, x16, gy.shape[2], gy.shape[3], K, C, R, S):
+        wtok.parts = _WgradJob(C, K, R, S, x16, gy, stride, pad, dil)  # launched with its group (flush_wgrads)
+        return _dummy_grad(wf)
+    if wtok is not None and wtok.uses == 1 and C * R * S * 4 <= PARTS_CONSUMER_LDS_BYTES:
+        wtok.parts = conv_wgrad_parts(x16, gy, K, R, S, stride, pad, dil)
+        return _dummy_grad(wf)          # the real gradient rides on the token (fp32 partials)
+    return conv_wgrad(x16, gy, K, R, S, stride, pad, dil)
+
+
+def _residual_grad(gy, rdt, res_token, res_up):
+    """step 4: the residual operand's gradient is dy - handed to the block's first conv's data gradient (``res_token``),
+    returned, or (``res_up``: the coarser FPN level's shape) summed 2 x 2"""
+    gres = res_token.hand_off(gy) if res_token is not None else gy.to(rdt)       # (handed over: None)
+    if res_up is not None:                    # d top[n, :, y, x] = sum of the 2 x 2 output gradients above it
+        g16 = _nhwc_bf16(gy)
+        gres = torch.empty(res_up, dtype=torch.bfloat16, device=gy.device, memory_format=torch.channels_last)
+        check(_lib.lib().oadg_fpn_topdown_bwd(ptr(g16), ptr(gres), g16.shape[0], g16.shape[2], g16.shape[3], res_up[2],
+                                              res_up[3], g16.shape[1], stream_ptr()), 'oadg_fpn_topdown_bwd')
+        gres = gres.to(rdt)
+    return gres
+
+
 class _Conv2dMFMA(torch.autograd.Function):
-    """y = [relu]( conv(x, wf) + bias [+ residual] ) in one kernel, on prepared bf16 weights.  Backward: ReLU mask +
-    bias gradient in one pass (or taken over by the consumer through ``out_token``), stride-1 data gradient on the
-    same kernel with ``wt`` (+ the producer's mask / bias gradient / identity gradient through ``in_token``),
-    weight gradient by csrc conv_wgrad256_kernel where it beats MIOpen, else aten (MIOpen)."""
+    """y = [relu]( conv(x, wf) + bias [+ residual] ) in one kernel, on prepared bf16 weights.  Backward, the four steps
+    above: ReLU mask + bias gradient in one pass (or taken over by the consumer through ``out_token``), data gradient on
+    the csrc kernels with ``wt`` (+ the producer's mask / bias gradient / identity gradient through ``in_token``, or left
+    on ``dep_token``), weight gradient by the csrc kernels; what is still needed then: ONE aten call (MIOpen)."""
 
     @staticmethod
     def forward(ctx, x, wf, bias, residual, wt, stride, pad, dil, relu, in_token, out_token, res_token, dep_token=None,
                 res_up=False):
         x16 = _nhwc_bf16(x)
         if in_token is not None and wt is not None and stride == 1:
-            in_token.armed = True           # this convolution's data gradient will finish the tensor's gradient
+            in_token.arm()                  # this convolution's data gradient will finish the tensor's gradient
+        if out_token is not None:
+            out_token.adopt()
         r16 = _nhwc_bf16(residual) if residual is not None else None
         bits = None
         if relu and out_token is not None and RELU_BITS and wf.shape[0] % 8 == 0:
@@ -1012,121 +1141,32 @@ class _Conv2dMFMA(torch.autograd.Function):
         x16, wf, wt, y = ctx.saved_tensors
         stride, pad, dil, has_bias, xdt, rdt = ctx.cfg
         in_token, out_token, res_token, dep_token = ctx.tokens
-        K, C, R, S = wf.shape
-        want_b = has_bias and ctx.needs_input_grad[2]
-        gb = None
-        if out_token is not None and out_token.grad_ptr is not None and out_token.grad_ptr == gy.data_ptr() and \
-                gy.dtype == torch.bfloat16 and gy.is_contiguous(memory_format=torch.channels_last):
-            gb = out_token.colsum if want_b else None     # masked and reduced by the consumer's dgrad epilogue
-            want_b = False
-            if pending_colsum(gb) is not None and not (ctx.wtoken is not None and ctx.wtoken.uses == 1):
-                resolve_colsum(gb)      # shared / unknown weights: autograd may sum this vector with others right away
-        elif (y is not None or want_b) and gy.dtype in (torch.bfloat16, torch.float32) and K % 8 == 0 and \
-                gy.is_contiguous(memory_format=torch.channels_last):
-            gy, gb = relu_bias_bwd(gy, y, want_b)            # mask + cast + bias gradient: one pass over dy
-            want_b = False
-        else:
-            gy = _nhwc_bf16(gy)
-            if y is not None:
-                gy = torch.ops.aten.threshold_backward(gy, y, 0)
-        if out_token is not None:
-            out_token.grad_ptr = out_token.colsum = None
         need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        gx = None
-        extra = None
-        if in_token is not None:
-            extra, in_token.extra = in_token.extra, None
-            in_token.closed = True
-        deposit = need_x and dep_token is not None and dep_token.armed and not dep_token.closed and DEPOSIT
-        if need_x and dep_token is not None and dep_token.closed:
-            # a depositor running AFTER the finisher: its gradient is returned and autograd adds it to the finisher's -
-            # possibly IN PLACE into the very tensor ``grad_ptr`` names (InputBuffer accumulates in place when it holds the
-            # last reference), which the pointer check of the producer could not see.  Taint the token: the producer then
-            # masks and reduces the summed gradient itself.
-            dep_token.grad_ptr = dep_token.colsum = None
-        if deposit:
-            # this tensor's gradient is finished by another convolution: add what was deposited so far in THIS launch's
-            # epilogue, leave the sum on the token, return nothing
-            dep_extra, dep_token.extra = dep_token.extra, None
-            if wt is not None and stride == 2 and R == 1 and dep_extra is not None:
-                gx = conv_dgrad_s2(gy, wt, x16.shape, R, accumulate=dep_extra)     # in place, on its strided grid
-            elif wt is not None and stride == 2:
-                gx = conv_dgrad_s2(gy, wt, x16.shape, R)
-                if dep_extra is not None:
-                    gx = gx + dep_extra
-            elif wt is not None:
-                gx = conv_forward(gy, wt, None, dep_extra, 1, dil * (R - 1) - pad, dil, False)
-            else:
-                gx = torch.ops.aten.convolution_backward(gy, x16, wf, None, [stride, stride], [pad, pad], [dil, dil],
-                                                         False, [0, 0], 1, [True, False, False])[0]
-                if dep_extra is not None:
-                    gx = gx + dep_extra.to(gx.dtype)
-            dep_token.extra = gx if gx.dtype == torch.bfloat16 else gx.to(torch.bfloat16)
-            gx = None
+        gy, gb, want_b = _incoming_grad(gy, y, out_token, ctx.wtoken, has_bias and ctx.needs_input_grad[2])
+        extra = in_token.close() if in_token is not None else None
+        gx = gw = None
+        if need_x and dep_token is not None and dep_token.may_deposit():
+            # finished by another convolution: add what was deposited so far in THIS epilogue, leave the sum, return nothing
+            dep_token.leave(_data_grad(gy, x16, wf, wt, stride, pad, dil, dep_token.take(), None, True)[0])
             need_x = False
-        if need_x and wt is not None and stride == 2:
-            # dx of the stride-2 layers (Bottleneck.conv2 / downsample of a stage's first block): parity-class convolutions
-            if in_token is not None and extra is None and in_token.masked:
-                mb = in_token.bits
-                gx, in_token.colsum = conv_dgrad_s2(gy, wt, x16.shape, R, mask=None if mb is not None else x16,
-                                                    want_colsum=True, mask_bits=mb)
-                in_token.grad_ptr = gx.data_ptr()
-            else:
-                gx = conv_dgrad_s2(gy, wt, x16.shape, R)
-            need_x = False
-        elif need_x and wt is not None:
-            # dx = conv(dy, rot180(W)^T) [+ identity gradient] [* (x > 0), column sums -> producer's bias gradient]
-            if in_token is not None:
-                mb = in_token.bits if in_token.masked else None
-                gx, in_token.colsum = conv_forward(gy, wt, None, extra, 1, dil * (R - 1) - pad, dil, False,
-                                                   mask=x16 if (mb is None and in_token.masked) else None,
-                                                   want_colsum=True, mask_bits=mb)
-                in_token.grad_ptr = gx.data_ptr()
-                extra = None
-            else:
-                gx = conv_forward(gy, wt, None, None, 1, dil * (R - 1) - pad, dil, False)
-            need_x = False
-        gw = None
-        if need_w and x16.numel() < 2 ** 32 and _hip_wgrad(K, C):
-            wtok = ctx.wtoken
-            if wtok is not None and wtok.uses == 1 and DEFER_WGRAD and \
-                    _group_sized(wtok.deferrable, x16, gy.shape[2], gy.shape[3], K, C, R, S):
-                wtok.parts = _WgradJob(C, K, R, S, x16, gy, stride, pad, dil)  # launched with its group (flush_wgrads)
-                gw = _dummy_grad(wf)
-            elif wtok is not None and wtok.uses == 1 and C * R * S * 4 <= PARTS_CONSUMER_LDS_BYTES:
-                wtok.parts = conv_wgrad_parts(x16, gy, K, R, S, stride, pad, dil)
-                gw = _dummy_grad(wf)          # the real gradient rides on the token (fp32 partials)
-            else:
-                gw = conv_wgrad(x16, gy, K, R, S, stride, pad, dil)
-            need_w = False
-            if want_b:
-                gb = gy.float().sum((0, 2, 3))
-                want_b = False
+        elif need_x:
+            gx, extra = _data_grad(gy, x16, wf, wt, stride, pad, dil, extra, in_token, False)
+            need_x = gx is None
+        if need_w:
+            gw = _weight_grad(ctx.wtoken, x16, wf, gy, stride, pad, dil)
+            need_w = gw is None
+            if want_b and not need_w:
+                gb, want_b = gy.float().sum((0, 2, 3)), False
         if need_x or need_w or want_b:
             outs = torch.ops.aten.convolution_backward(
-                gy, x16, wf, [K] if has_bias else None, [stride, stride], [pad, pad], [dil, dil], False, [0, 0],
+                gy, x16, wf, [wf.shape[0]] if has_bias else None, [stride, stride], [pad, pad], [dil, dil], False, [0, 0],
                 1, [need_x, need_w, want_b])
-            if gx is None:
-                gx = outs[0]
-            if outs[1] is not None:
-                gw = outs[1]
-            if outs[2] is not None:
-                gb = outs[2].float()
+            gx = outs[0] if gx is None else gx
+            gw = outs[1] if outs[1] is not None else gw
+            gb = outs[2].float() if outs[2] is not None else gb
         if gx is not None and extra is not None:      # library data gradient: the identity gradient is added here
             gx = gx + extra.to(gx.dtype)
-        gres = None
-        if rdt is not None and ctx.needs_input_grad[3]:
-            if res_token is not None:
-                res_token.extra = gy                  # folded into the block's first conv's data gradient
-            else:
-                gres = gy.to(rdt)
-            if ctx.res_up is not None:
-                ts = ctx.res_up                   # d top[n, :, y, x] = sum of the 2 x 2 output gradients above it
-                g16 = _nhwc_bf16(gy)
-                gres = torch.empty(ts, dtype=torch.bfloat16, device=gy.device, memory_format=torch.channels_last)
-                check(_lib.lib().oadg_fpn_topdown_bwd(ptr(g16), ptr(gres), g16.shape[0], g16.shape[2], g16.shape[3], ts[2],
-                                                      ts[3], g16.shape[1], stream_ptr()), 'oadg_fpn_topdown_bwd')
-                gres = gres.to(rdt)
+        gres = _residual_grad(gy, rdt, res_token, ctx.res_up) if rdt is not None and ctx.needs_input_grad[3] else None
         return (gx.to(xdt) if gx is not None else None), gw, gb, gres, None, None, None, None, None, None, None, None, None, None
 
 
@@ -1174,7 +1214,7 @@ class _NarrowHead(torch.autograd.Function):
             x16 = _nhwc_bf16(x)
             N, C, H, W = x16.shape
             if tok is not None:
-                tok.armed = True
+                tok.arm()
             y = torch.empty((N, 16, H, W), dtype=torch.bfloat16, device=x16.device, memory_format=torch.channels_last)
             check(_n16_launch('fwd', N * H * W, C, 0.0, lambda: L.oadg_conv1x1_n16_fwd(
                 ptr(x16), ptr(w16), ptr(b16), ptr(y), N * H * W, C, stream_ptr())), 'oadg_conv1x1_n16_fwd')
@@ -1198,10 +1238,7 @@ class _NarrowHead(torch.autograd.Function):
         Ms = [x.shape[0] * x.shape[2] * x.shape[3] for x in xs16]
         gxs = []
         for l, (x16, gy, tok, M) in enumerate(zip(xs16, gys, ctx.toks, Ms)):
-            extra = None
-            if tok is not None:
-                extra, tok.extra = tok.extra, None
-                tok.closed = True
+            extra = tok.close() if tok is not None else None
             if not ctx.needs_input_grad[6 + l]:
                 gxs.append(None)
                 continue
@@ -1213,8 +1250,7 @@ class _NarrowHead(torch.autograd.Function):
                               lambda: L.oadg_conv1x1_n16_dgrad(ptr(gy), ptr(wt16), ptr(gx), ptr(mb) if finish else None,
                                                                ptr(part), M, C, stream_ptr())), 'oadg_conv1x1_n16_dgrad')
             if finish:
-                tok.colsum = _colsum(part, C)
-                tok.grad_ptr = gx.data_ptr()
+                tok.finish(gx, _colsum(part, C))
             elif extra is not None:
                 gx = gx + extra               # (another consumer deposited a gradient: the producer masks / reduces the sum)
             gxs.append(gx.to(xdts[l]))
@@ -1256,26 +1292,22 @@ def _applies(x, weight, stride, padding, dilation):
 
 
 def conv2d(x, weight, bias, stride, padding, dilation, relu=False, residual=None, owner=None, in_token=None,
-           out_token=None, res_token=None, dep_token=None, res_up=False):
-    """layers.conv2d implementation hook: returns None for shapes the kernel does not cover."""
+           out_token=None, res_token=None, dep_token=None, res_up=False, bn=None):
+    """layers.conv2d implementation hook: returns None for shapes the kernel does not cover.  ``bn``: see conv_bn"""
     stride, padding, dilation = _norm3(stride, padding, dilation)
     if not _applies(x, weight, stride, padding, dilation):
         return None
     K, C, R, S = weight.shape
-    wf, b, wt = prepared(weight, None, bias, _wt_useful(x, K, C, stride[0], padding[0], dilation[0], R), owner)
+    wf, b, wt = prepared(weight, bn, bias, _wt_useful(x, K, C, stride[0], padding[0], dilation[0], R), owner)
     return _Conv2dMFMA.apply(x, wf, b, residual, wt, stride[0], padding[0], dilation[0], bool(relu), in_token,
                              out_token, res_token, dep_token, bool(res_up))
 
 
-def conv_bn(x, conv, bn, relu=False, residual=None, in_token=None, out_token=None, res_token=None, dep_token=None):
+def conv_bn(x, conv, bn, relu=False, residual=None, **tokens):
     """layers.conv_bn implementation hook (eval-mode BN folded by the preparation kernel)."""
-    stride, padding, dilation = _norm3(conv.stride, conv.padding, conv.dilation)
-    if bn.training or conv.bias is not None or not _applies(x, conv.weight, stride, padding, dilation):
+    if bn.training or conv.bias is not None:
         return None
-    K, C, R, S = conv.weight.shape
-    wf, b, wt = prepared(conv.weight, bn, None, _wt_useful(x, K, C, stride[0], padding[0], dilation[0], R), conv)
-    return _Conv2dMFMA.apply(x, wf, b, residual, wt, stride[0], padding[0], dilation[0], bool(relu), in_token,
-                             out_token, res_token, dep_token)
+    return conv2d(x, conv.weight, None, conv.stride, conv.padding, conv.dilation, relu, residual, conv, bn=bn, **tokens)
 
 
 FUSED_FROZEN_BLOCK = os.environ.get('OADG_FUSED_FROZEN_BLOCK', '1') == '1'
@@ -1288,8 +1320,7 @@ def frozen_bottleneck(x, block):
     launches move 2 - 4x the bytes (resnet.py:263-302 under _freeze_stages).  Returns None when the block / input is not
     of that kind - the caller runs its convolutions one by one.  No autograd graph: nothing upstream of a frozen block
     needs a gradient."""
-    if not (ENABLED and FUSED_FROZEN_BLOCK and x.is_cuda and x.dim() == 4 and not x.requires_grad and
-            (x.dtype == torch.bfloat16 or torch.is_autocast_enabled())):
+    if not (on_path(x) and FUSED_FROZEN_BLOCK and x.dim() == 4 and not x.requires_grad):
         return None
     c1, c2, c3 = block.conv1, block.conv2, block.conv3
     ds = block.downsample
@@ -1339,18 +1370,17 @@ def frozen_bottleneck(x, block):
 ENABLED = False
 
 
+def on_path(x):
+    """is ``x`` on the bf16 MFMA path: kernels enabled, a device tensor, bf16 itself or under autocast?"""
+    return ENABLED and x.is_cuda and (x.dtype == torch.bfloat16 or torch.is_autocast_enabled())
+
+
 def tokens_ok(x, *convs):
     """may GradTokens be threaded through these convolutions of input x?  (all of them on the MFMA path, bf16/autocast,
     eval-mode BN folded, gradients flowing)"""
-    if not (ENABLED and x.is_cuda and torch.is_grad_enabled()):
+    if not (on_path(x) and torch.is_grad_enabled()):
         return False
-    for c in convs:
-        st, pd, dl = _norm3(c.stride, c.padding, c.dilation)
-        K, C, R, S = c.weight.shape
-        if c.bias is not None or C % 64 or K % 64 or st[0] != st[1] or pd[0] != pd[1] or dl[0] != dl[1] or \
-                c.weight.shape[2] != c.weight.shape[3] or not (x.dtype == torch.bfloat16 or torch.is_autocast_enabled()):
-            return False
-    return True
+    return all(c.bias is None and supported(x, c.weight, *_norm3(c.stride, c.padding, c.dilation)) for c in convs)
 
 
 def enable(on=True):

@@ -560,17 +560,7 @@ def _deposit(tokens, grads):
     not yet closed): leave this part on the token - that launch adds it in its epilogue - and return nothing."""
     if tokens is None:
         return grads
-    from . import hip_conv
-    out = []
-    for tok, g in zip(tokens, grads):
-        if tok is not None and hip_conv.DEPOSIT and tok.armed and not tok.closed and g.dtype == torch.bfloat16:
-            tok.extra = g if tok.extra is None else tok.extra + g
-            out.append(None)
-        else:
-            if tok is not None and tok.closed:
-                tok.grad_ptr = tok.colsum = None        # late depositor: the producer must not trust the finisher's result
-            out.append(g)
-    return out
+    return [None if tok is not None and tok.deposit(g) else g for tok, g in zip(tokens, grads)]
 
 
 # ------------------------------------------------------------------------------- FPN top-down

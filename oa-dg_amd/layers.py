@@ -65,20 +65,11 @@ def conv_bn(x, conv, bn, relu=False, residual=None, **tokens):
         y = _CONV_BN_IMPL(x, conv, bn, relu, residual, **tokens)
         if y is not None:
             return y
-    frozen = not (conv.weight.requires_grad or bn.weight.requires_grad or bn.bias.requires_grad)
-    key = None
-    if frozen:   # constant until the parameters/buffers are overwritten: fold once
-        key = (conv.weight._version, bn.weight._version, bn.bias._version, bn.running_mean._version,
-               bn.running_var._version, conv.weight.device, conv.weight.data_ptr())
-        cached = getattr(conv, '_folded', None)
-        if cached is not None and cached[0] == key:
-            return conv2d(x, cached[1], cached[2], conv.stride, conv.padding, conv.dilation, relu, residual)
-    scale = bn.weight * torch.rsqrt(bn.running_var + bn.eps)
-    w = conv.weight * scale.view(-1, 1, 1, 1)
-    b = bn.bias - bn.running_mean * scale
-    if frozen:
-        w, b = w.detach(), b.detach()
-        conv._folded = (key, w, b)
+    if not (conv.weight.requires_grad or bn.weight.requires_grad or bn.bias.requires_grad):
+        w, b = folded_frozen(conv, bn)   # constant until the parameters/buffers are overwritten: fold once
+    else:
+        scale = bn.weight * torch.rsqrt(bn.running_var + bn.eps)
+        w, b = conv.weight * scale.view(-1, 1, 1, 1), bn.bias - bn.running_mean * scale
     return conv2d(x, w, b, conv.stride, conv.padding, conv.dilation, relu, residual)
 
 

@@ -5,7 +5,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import hip_ops, layers
+from . import hip_conv, hip_ops, layers
 
 from .layers import ConvModule, xavier_init
 from .registry import NECKS
@@ -74,24 +74,20 @@ class FPN(nn.Module):
         # the level's gradient (RoIAlign deposits its part on the token, hip_ops.roi_align_fpn) and hands this
         # convolution its bias gradient as the column sums of that launch.  Not for the level the extra levels are
         # subsampled from (a third consumer).
-        from . import hip_conv
-        if token and not (conv.with_norm or conv.with_activation) and hip_conv.ENABLED and x.is_cuda and \
-                torch.is_grad_enabled() and (x.dtype == torch.bfloat16 or torch.is_autocast_enabled()):
+        if token and not (conv.with_norm or conv.with_activation) and hip_conv.on_path(x) and torch.is_grad_enabled():
             c = conv.conv
             tok = hip_conv.GradToken(masked=False)
             y = layers.conv2d(x, c.weight, c.bias, c.stride, c.padding, c.dilation, out_token=tok, in_token=in_token,
                               owner=c)
-            if getattr(y.grad_fn, 'name', lambda: '')().startswith('_Conv2dMFMA'):
+            if tok.produced(y):
                 y._oadg_token = tok
             return y
         return conv(x)
 
     def forward(self, inputs):
         assert len(inputs) == len(self.in_channels)
-        from . import hip_conv
         x0 = inputs[self.start_level]
-        t_lat0 = hip_conv.GradToken(masked=False) if (hip_conv.ENABLED and x0.is_cuda and torch.is_grad_enabled() and
-                                                      (x0.dtype == torch.bfloat16 or torch.is_autocast_enabled())) else None
+        t_lat0 = hip_conv.GradToken(masked=False) if hip_conv.on_path(x0) and torch.is_grad_enabled() else None
         n = len(self.lateral_convs)
         laterals = [None] * n
         for i in range(n - 1, -1, -1):
@@ -104,7 +100,6 @@ class FPN(nn.Module):
             y = None
             if top is not None and self.upsample_cfg.get('mode') == 'nearest' and 'scale_factor' not in self.upsample_cfg \
                     and not (conv.with_norm or conv.with_activation) and \
-                    (x.dtype == torch.bfloat16 or torch.is_autocast_enabled()) and \
                     hip_conv.topdown_ok(x, conv.conv.out_channels, top):
                 c = conv.conv
                 y = hip_conv.conv2d(x, c.weight, c.bias, c.stride, c.padding, c.dilation, residual=top, owner=c,

@@ -849,6 +849,71 @@ def test_grad_token_late_depositor_taints_the_token(dev):
         hip_conv.enable(False)
 
 
+@pytest.mark.parametrize('case', ['s2_3x3_deposit', 'library_deposit', 's2_finisher_with_identity'])
+def test_grad_token_data_gradient_forms_off_the_model_path(dev, monkeypatch, case):
+    """The data-gradient forms of _Conv2dMFMA.backward that the detector's own graphs do not reach, each against the same
+    network without any token (the comparison and tolerance of the late-depositor test above).  t = relu(P(x)):
+    s2_3x3_deposit - a 3x3 / stride-2 DEPOSITOR that finds a deposit: stride-2 kernel, then a torch add;
+    library_deposit - a depositor without a second weight copy (S2_DGRAD off): library data gradient, then a torch add;
+    s2_finisher_with_identity - a stride-2 FINISHER that receives an identity-path gradient: the plain stride-2 kernel,
+    the identity gradient added by torch, and P masks / reduces the sum itself (nothing was finished).
+    Maps of 13 x 21 (parity classes of unequal extents); N * H * W = 546 is no multiple of a tile."""
+    import torch.nn as nn
+    from oadg_amd import hip_conv, layers
+    hip_conv.enable(True)
+    try:
+        torch.manual_seed(3)
+        monkeypatch.setattr(hip_conv, 'S2_DGRAD', case != 'library_deposit')
+        cl = dict(memory_format=torch.channels_last)
+
+        def conv_bn(cin, cout, k, stride=1):
+            c = nn.Conv2d(cin, cout, k, stride=stride, padding=k // 2, bias=False).to(dev).to(**cl)
+            bn = nn.BatchNorm2d(cout).to(dev).eval()
+            with torch.no_grad():
+                bn.weight.uniform_(0.5, 1.5); bn.bias.normal_(0, 0.3); bn.running_var.uniform_(0.5, 1.5); bn.running_mean.normal_(0, 0.3)
+            return c, bn
+        P, F_ = conv_bn(64, 128, 3), conv_bn(128, 64, 3, 2 if case == 's2_finisher_with_identity' else 1)
+        D1, D2 = conv_bn(128, 128, 1), conv_bn(128, 128, 3 if case == 's2_3x3_deposit' else 1, 2)
+        G = conv_bn(64, 128, 1)
+        mods = (P, F_, G) if case == 's2_finisher_with_identity' else (P, F_, D1, D2)
+        params = [p for c, bn in mods for p in list(c.parameters()) + list(bn.parameters())]
+        x = torch.randn(2, 64, 13, 21, device=dev).bfloat16().contiguous(**cl)
+        calls = []
+        orig = hip_conv.conv_dgrad_s2
+        monkeypatch.setattr(hip_conv, 'conv_dgrad_s2', lambda *a, **k: (calls.append((a[3], sorted(k))), orig(*a, **k))[1])
+        res = {}
+        for mode in ('tokens', 'plain'):
+            for p in params:
+                p.grad = None
+            del calls[:]
+            xin = x.clone().requires_grad_(True)
+            tok = hip_conv.GradToken() if mode == 'tokens' else None
+            kw = (lambda **k: k) if tok is not None else (lambda **k: {})
+            with torch.autocast('cuda', dtype=torch.bfloat16):
+                t = layers.conv_bn(xin, *P, relu=True, **kw(out_token=tok))
+                ys = [layers.conv_bn(t, *F_, **kw(in_token=tok))]                     # the finisher FIRST: its backward is last
+                if case == 's2_finisher_with_identity':
+                    ys.append(layers.conv_bn(xin, *G, residual=t, **kw(res_token=tok)))
+                else:
+                    ys.append(layers.conv_bn(t, *D2, **kw(dep_token=tok)))            # finds D1's deposit
+                    ys.append(layers.conv_bn(t, *D1, **kw(dep_token=tok)))            # 1x1 / stride 1: deposits first
+            if mode == 'tokens':
+                gs = [torch.randn(y.shape, device=dev).bfloat16().contiguous(**cl) for y in ys]
+            torch.autograd.backward(ys, gs)
+            if tok is not None:
+                assert tok.adopted and tok.closed and tok.extra is None and tok.grad_ptr is None
+                # (stride-2 launches of this graph: R and the keyword operands - none masks, sums or accumulates in place)
+                assert calls == {'s2_3x3_deposit': [(3, [])], 'library_deposit': [],
+                                 's2_finisher_with_identity': [(3, [])]}[case]
+            res[mode] = {i: p.grad.float().clone() for i, p in enumerate(params)}
+            res[mode]['x'] = xin.grad.float().clone()
+        for k in res['plain']:
+            a, b = res['tokens'][k], res['plain'][k]
+            assert (a - b).abs().max().item() <= 3e-2 * b.abs().max().item() + 1e-6, (case, k)
+    finally:
+        hip_conv.enable(False)
+
+
 def test_deferred_column_sums_give_the_same_gradients_bit_for_bit(dev):
     """hip_conv.DEFER_COLSUM (TrainEngine's backward): the per-layer reductions of the bias-gradient partial sums run as
     ONE launch after the backward pass (oadg_colsum_reduce_multi), BN scale gradients are left raw by the weight
