@@ -345,6 +345,32 @@ int oadg_instance_change_points(const uint16_t* maps, int n, int H, int W, int m
                                 int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * VOC-protocol evaluation: true / false positive assignment of a whole test split (csrc/voc_eval.hip)
+ *   replaces tpfp_default   mmdet/core/evaluation/mean_ap.py:168-267 (area_ranges=None), run per (image, class) by a process
+ *            pool (mean_ap.py:357-380), and bbox_overlaps  mmdet/core/evaluation/bbox_overlaps.py:5-65
+ * A segment is one (image, class) pair, n_seg of them.  dets: fp32 [n_det][5] = x1, y1, x2, y2, score, concatenated in
+ * segment order; det_off: int32 [n_seg + 1], the start of every segment in dets; gts: fp32 [n_gt][4], 16-byte aligned, per
+ * segment the regular boxes first and the ignored ("difficult") ones after; gt_off: int32 [n_seg + 1]; gt_reg: int32 [n_seg],
+ * the number of regular boxes of the segment.  Offsets are clamped to the arrays' extents before use.
+ * iou_thrs_host: n_thr <= OADG_VOC_MAX_THRS thresholds in HOST memory (read during the call); legacy != 0: widths and heights
+ * are x2 - x1 + 1 (mmdet 1.x / the VOC devkit), in the IoU too.
+ *   iou_max [n_det]: per detection the largest fp32 IoU with the boxes of its segment, computed in the operation order of
+ *     bbox_overlaps.py without contraction, correctly rounded; iou_arg [n_det]: the lowest index (within the segment) that
+ *     attains it, -1 (and iou_max 0) when the segment has no box.
+ *   flags: uint8 [n_thr][n_det].  0: iou_max >= thr and the best box is an ignored one (neither tp nor fp); 1: iou_max >= thr,
+ *     the best box is regular and this detection has the highest score among those that chose it (equal scores: the lowest
+ *     index in the segment) - the true positive; 2: every other detection - the false positives.  Independent of the order
+ *     of arrival: the same bytes from run to run.  Every element of the three outputs is written.
+ * The workspace (8-byte aligned) must hold oadg_voc_tpfp_workspace_bytes(...) bytes (0: arguments the call refuses);
+ * OADG_ESIZE when it is smaller.  One launch for the split and all thresholds.  Called from oadg_voc_tpfp.py only (the device half
+ * of evaluation.eval_map_voc(device=...)). */
+#define OADG_VOC_MAX_THRS 8
+size_t oadg_voc_tpfp_workspace_bytes(int n_seg, int n_det, int n_gt, int n_thr);
+int oadg_voc_tpfp(const float* dets, const int32_t* det_off, const float* gts, const int32_t* gt_off, const int32_t* gt_reg,
+                  int n_seg, int n_det, int n_gt, const float* iou_thrs_host, int n_thr, int legacy, float* iou_max,
+                  int32_t* iou_arg, uint8_t* flags, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * PNG output: a resident batch -> the zlib stream of every image, and the stream -> a file (csrc/png_encode.hip)
  *   replaces save_data  tools/analysis_tools/get_corrupted_dataset.py:83-113 (PIL.Image.fromarray(img).save(path): PNG row
  *            filtering and zlib deflate of every corrupted image on one host core)

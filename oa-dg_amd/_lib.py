@@ -63,6 +63,7 @@ class RoiSampleImage(Structure):
 ROI_SAMPLE_MAX_IMAGES = 8
 RPN_MAX_LEVELS = 8
 PARSE_LOSSES_MAX = 32
+VOC_MAX_THRS = 8
 
 
 class RegionOp(Structure):
@@ -245,6 +246,8 @@ SIGNATURES = {
     'oadg_instance_maps_workspace_bytes': (cs, [ci, ci, ci]),
     'oadg_instance_stats': (ci, [vp, ci, ci, ci, ci, vp, ci, vp, vp, cs, vp]),
     'oadg_instance_change_points': (ci, [vp, ci, ci, ci, ci, vp, ci, vp, vp, cs, vp]),
+    'oadg_voc_tpfp_workspace_bytes': (cs, [ci, ci, ci, ci]),
+    'oadg_voc_tpfp': (ci, [vp, vp, vp, vp, vp, ci, ci, ci, POINTER(cf), ci, ci, vp, vp, vp, vp, cs, vp]),
     'oadg_png_encode_stream_capacity': (cs, [ci, ci]),
     'oadg_png_encode_segments': (ci, [ci, ci]),
     'oadg_png_encode_workspace_bytes': (cs, [ci, ci, ci]),

@@ -12,6 +12,7 @@ into one pinned coefficient buffer, one upload carries it to the device and the 
 byte-equal to PIL.  ``XMLDataset`` / ``SdgodDataset`` (mmdet/datasets/{xml_style,sdgod}.py: VOC-style id lists, XML
 annotations, JPEG frames - the Diverse-Weather benchmark) reuse all of it.
 """
+import bisect
 import json
 import os
 import threading
@@ -410,8 +411,9 @@ class XMLDataset(CocoDataset):
 
 @DATASETS.register_module()
 class SdgodDataset(XMLDataset):
-    """sdgod.py:12-29: the Diverse-Weather (S-DGOD) classes; the year is inferred from ``img_prefix``.  ``evaluate`` is
-    XMLDataset's: ``eval_map`` in area mode (the 11-point VOC07 protocol of sdgod.py:67-70 is not restated)."""
+    """sdgod.py:12-106: the Diverse-Weather (S-DGOD) classes; the year is inferred from ``img_prefix``.  ``evaluate`` is the
+    reference's VOC protocol (evaluation.sdgod_evaluate): legacy "+ 1" coordinates, ``difficult`` objects as ignore regions
+    and, for a VOC2007 prefix, the 11-point AP - matched on the GPU (csrc/voc_eval.hip) when there is one."""
     CLASSES = ('bus', 'bike', 'car', 'motor', 'person', 'rider', 'truck')
 
     def __init__(self, **kwargs):
@@ -422,6 +424,9 @@ class SdgodDataset(XMLDataset):
             self.year = 2012
         else:
             raise ValueError('Cannot infer dataset year from img_prefix')
+
+    def evaluate(self, results, metric='mAP', logger=None, **eval_kwargs):
+        return evaluation.sdgod_evaluate(self, results, metric=metric, logger=logger, **eval_kwargs)
 
 
 @DATASETS.register_module()
@@ -445,8 +450,56 @@ class RepeatDataset:
         return self.dataset.get_ann_info(idx % self._ori_len)
 
 
+@DATASETS.register_module()
+class ConcatDataset:
+    """dataset_wrappers.py:17-134 ConcatDataset: the datasets one after the other (length, ``batch``, ``get_ann_info``,
+    the concatenated group flag) and ``evaluate`` with ``separate_eval=True``: every dataset on its own slice of the
+    results, its keys prefixed ``{i}_``.  Evaluating the concatenation as a whole is not built."""
+
+    def __init__(self, datasets, separate_eval=True):
+        if not separate_eval:
+            raise NotImplementedError("ConcatDataset(separate_eval=False) is not built")
+        self.datasets, self.separate_eval = list(datasets), separate_eval
+        self.CLASSES = getattr(self.datasets[0], 'CLASSES', None)
+        self.cumulative_sizes = np.cumsum([len(d) for d in self.datasets]).tolist()
+        if hasattr(self.datasets[0], 'flag'):
+            self.flag = np.concatenate([d.flag for d in self.datasets])
+
+    def __len__(self):
+        return self.cumulative_sizes[-1]
+
+    def _locate(self, idx):
+        if idx < 0:
+            if -idx > len(self):
+                raise ValueError('absolute value of index should not exceed dataset length')
+            idx = len(self) + idx
+        k = bisect.bisect_right(self.cumulative_sizes, idx)
+        return k, idx - (self.cumulative_sizes[k - 1] if k else 0)
+
+    def get_ann_info(self, idx):
+        k, i = self._locate(idx)
+        return self.datasets[k].get_ann_info(i)
+
+    def batch(self, indices):
+        """one batch from ONE of the datasets (an image shape per batch, and a dataset per batch)"""
+        where = [self._locate(i) for i in indices]
+        assert len({k for k, _ in where}) == 1, 'a batch does not cross the seam between two concatenated datasets'
+        return self.datasets[where[0][0]].batch([i for _, i in where])
+
+    def evaluate(self, results, logger=None, **kwargs):
+        assert len(results) == len(self), f'Dataset and results have different sizes: {len(self)} v.s. {len(results)}'
+        total = {}
+        for k, ds in enumerate(self.datasets):
+            start = self.cumulative_sizes[k - 1] if k else 0
+            for name, v in ds.evaluate(results[start:self.cumulative_sizes[k]], logger=logger, **kwargs).items():
+                total[f'{k}_{name}'] = v
+        return total
+
+
 def _files_present(cfg):
     ann = cfg.get('ann_file')
+    if isinstance(ann, (list, tuple)):
+        return all(_files_present(dict(cfg, ann_file=a)) for a in ann)
     if ann is None:
         return True
     root = cfg.get('data_root')
@@ -454,9 +507,9 @@ def _files_present(cfg):
 
 
 def build_dataset(cfg, default_args=None, synthetic_fallback=False):
-    """datasets/builder.py:54-77 (RepeatDataset + plain datasets).  ``synthetic_fallback``: a dataset whose annotation
-    file does not exist on this machine (an unmodified reference config on a box without Cityscapes) is replaced by
-    the Cityscapes-shaped synthetic source, loudly."""
+    """datasets/builder.py:31-82 (RepeatDataset, a list-valued ``ann_file`` -> ConcatDataset, plain datasets).
+    ``synthetic_fallback``: a dataset whose annotation file does not exist on this machine (an unmodified reference
+    config on a box without Cityscapes) is replaced by the Cityscapes-shaped synthetic source, loudly."""
     cfg = dict(cfg)
     if cfg.get('type') == 'RepeatDataset' and synthetic_fallback and not _files_present(cfg['dataset']):
         cfg = dict(cfg['dataset'])          # one synthetic pass is as good as eight
@@ -470,4 +523,15 @@ def build_dataset(cfg, default_args=None, synthetic_fallback=False):
         return SyntheticCityscapes(pipeline=cfg.get('pipeline'), **keep)
     if cfg.get('type') == 'RepeatDataset':
         return RepeatDataset(build_dataset(cfg['dataset'], default_args, synthetic_fallback), cfg['times'])
+    if isinstance(cfg.get('ann_file'), (list, tuple)):          # builder.py:31-55 _concat_dataset
+        prefixes = cfg.get('img_prefix')
+        parts = []
+        for i, ann in enumerate(cfg['ann_file']):
+            one = {k: v for k, v in cfg.items() if k != 'separate_eval'}
+            one['ann_file'] = ann
+            if isinstance(prefixes, (list, tuple)):
+                assert len(prefixes) == len(cfg['ann_file']), 'one img_prefix per ann_file (or one string for all)'
+                one['img_prefix'] = prefixes[i]
+            parts.append(build_dataset(one, default_args))
+        return ConcatDataset(parts, cfg.get('separate_eval', True))
     return build_from_cfg(cfg, DATASETS, default_args)

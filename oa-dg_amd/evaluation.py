@@ -7,8 +7,16 @@ tools/analysis_tools/robustness_eval.py:37-118 and test_robustness.py:28-64.  py
 this file restates COCOeval's published algorithm for iouType 'bbox' (evaluateImg / accumulate / summarize): the greedy
 score-ordered matching with crowd and area-range "ignore" regions, the 101-point interpolated precision envelope, and
 the twelve summary numbers.  It is pinned by hand-computed cases (tests/test_evaluation.py), not by pycocotools.
+
+The VOC protocol of the Diverse-Weather benchmark (``SdgodDataset.evaluate`` -> mmdet/core/evaluation/mean_ap.py ``eval_map``
+with 'voc07' and the legacy coordinates) is ``eval_map_voc`` below: host functions pinned to the reference's own output
+(tests/golden/voc_eval_reference.npz) and the same matching on the GPU (csrc/voc_eval.hip).
 """
+import os
+
 import numpy as np
+
+from ._lib import VOC_MAX_THRS                # thresholds of one device call (oadg_voc_tpfp)
 
 IOU_THRS = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)
 REC_THRS = np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True)
@@ -164,8 +172,20 @@ def dataset_gt_anns(dataset, indices=None):
 
 
 # ------------------------------------------------------------------------------------------ VOC-style mAP
-def average_precision(recalls, precisions):
-    """mean_ap.py:13-56, mode='area'."""
+def average_precision(recalls, precisions, mode='area'):
+    """mean_ap.py:13-56 for one scale.  'area': the area under the precision envelope; '11points' (mean_ap.py:45-52, the
+    VOC07 protocol): the mean of the best precision at recall >= 0, 0.1, ..., 1, accumulated in fp32 as the reference's
+    ``ap`` array does."""
+    if mode == '11points':
+        recalls, precisions = np.asarray(recalls), np.asarray(precisions)
+        ap = np.zeros(1, dtype=np.float32)
+        for thr in np.arange(0, 1 + 1e-3, 0.1):
+            precs = precisions[recalls >= thr]
+            ap[0] += precs.max() if precs.size > 0 else 0
+        ap /= 11
+        return float(ap[0])
+    if mode != 'area':
+        raise ValueError('Unrecognized mode, only "area" and "11points" are supported')
     mrec = np.concatenate([[0.0], recalls, [1.0]])
     mpre = np.concatenate([[0.0], precisions, [0.0]])
     for i in range(len(mpre) - 1, 0, -1):
@@ -222,6 +242,205 @@ def dataset_box_anns(dataset, indices=None):
     return anns
 
 
+# ------------------------------------------------------------------------------------------ the reference's VOC protocol
+# mean_ap.py:168-267, 297-440 and bbox_overlaps.py as SdgodDataset.evaluate drives them (sdgod.py:65-89): fp32 IoU with the
+# legacy "+ 1" extents, difficult / min_size boxes as "ignore" regions, the 11-point AP for a VOC2007 prefix.  The host
+# functions below are the yardstick (pinned to the reference's own output by tests/golden/voc_eval_reference.npz) and the
+# path without a GPU; csrc/voc_eval.hip computes the same flags for a whole split in one launch.  Two rules are FIXED here
+# where the reference leaves them to numpy: equal scores are ordered lowest index first (a stable
+# sort, per image and in the per-class accumulation), and the threshold is rounded to fp32 and compared in fp32.
+FLAG_IGNORED, FLAG_TP, FLAG_FP = 0, 1, 2
+
+
+def bbox_overlaps_voc(b1, b2, use_legacy_coordinate=False):
+    """bbox_overlaps.py:5-65, mode 'iou': fp32 [n, k], every operation in the reference's order (numpy fuses nothing)"""
+    b1 = np.asarray(b1).astype(np.float32).reshape(-1, 4)
+    b2 = np.asarray(b2).astype(np.float32).reshape(-1, 4)
+    ex = np.float32(1.0 if use_legacy_coordinate else 0.0)
+    if b1.shape[0] * b2.shape[0] == 0:
+        return np.zeros((b1.shape[0], b2.shape[0]), dtype=np.float32)
+    area1 = (b1[:, 2] - b1[:, 0] + ex) * (b1[:, 3] - b1[:, 1] + ex)
+    area2 = (b2[:, 2] - b2[:, 0] + ex) * (b2[:, 3] - b2[:, 1] + ex)
+    x_start = np.maximum(b1[:, None, 0], b2[None, :, 0])
+    y_start = np.maximum(b1[:, None, 1], b2[None, :, 1])
+    x_end = np.minimum(b1[:, None, 2], b2[None, :, 2])
+    y_end = np.minimum(b1[:, None, 3], b2[None, :, 3])
+    overlap = np.maximum(x_end - x_start + ex, np.float32(0)) * np.maximum(y_end - y_start + ex, np.float32(0))
+    union = np.maximum(area1[:, None] + area2[None, :] - overlap, np.float32(1e-6))
+    return overlap / union
+
+
+def voc_match(dets, gts_all, use_legacy_coordinate=False):
+    """per detection the largest IoU with the boxes of its (image, class) and the FIRST box that attains it
+    (mean_ap.py:231-236): (iou_max fp32 [m], iou_arg int32 [m]); (0, -1) where there is no box"""
+    m = len(dets)
+    if len(gts_all) == 0 or m == 0:
+        return np.zeros(m, dtype=np.float32), np.full(m, -1, dtype=np.int32)
+    ious = bbox_overlaps_voc(np.asarray(dets)[:, :4], gts_all, use_legacy_coordinate)
+    return ious.max(axis=1), ious.argmax(axis=1).astype(np.int32)
+
+
+def voc_flags(dets, gts_all, n_regular, iou_thr, use_legacy_coordinate=False, match=None):
+    """mean_ap.py:196-267 with area_ranges=None for one (image, class): ``gts_all`` = the regular boxes followed by the
+    ignored ones, the first ``n_regular`` of them regular.  uint8 [m]: FLAG_TP, FLAG_FP, or FLAG_IGNORED for a detection
+    whose best box is an ignored one.  ``match``: ``voc_match`` of the same boxes, when the caller has it (it does not
+    depend on the threshold)."""
+    dets = np.asarray(dets, dtype=np.float32).reshape(-1, 5)
+    flags = np.full(len(dets), FLAG_FP, dtype=np.uint8)
+    if len(gts_all) == 0 or len(dets) == 0:          # (mean_ap.py:220-229: only with no regular AND no ignored box)
+        return flags
+    iou_max, iou_arg = voc_match(dets, gts_all, use_legacy_coordinate) if match is None else match
+    thr = np.float32(iou_thr)
+    covered = np.zeros(len(gts_all), dtype=bool)
+    for i in np.argsort(-dets[:, 4], kind='stable'):
+        if iou_max[i] >= thr:
+            g = iou_arg[i]
+            if g >= n_regular:
+                flags[i] = FLAG_IGNORED
+            elif not covered[g]:
+                covered[g] = True
+                flags[i] = FLAG_TP
+    return flags
+
+
+def tpfp_default(dets, gts, gts_ignore=None, iou_thr=0.5, use_legacy_coordinate=False):
+    """mean_ap.py:168-267 (area_ranges=None): (tp, fp) fp32 [m] of 0 / 1"""
+    gts = np.asarray(gts, dtype=np.float32).reshape(-1, 4)
+    ign = np.zeros((0, 4), np.float32) if gts_ignore is None else np.asarray(gts_ignore, dtype=np.float32).reshape(-1, 4)
+    flags = voc_flags(dets, np.vstack((gts, ign)), len(gts), iou_thr, use_legacy_coordinate)
+    return (flags == FLAG_TP).astype(np.float32), (flags == FLAG_FP).astype(np.float32)
+
+
+def pack_voc_segments(results, annotations, num_classes):
+    """a split as the arrays of oadg_voc_tpfp: one segment per (image, class), s = image * num_classes + class.
+    dict(dets fp32 [D, 5], det_off int32 [S + 1], gts fp32 [G, 4] - per segment the regular boxes, then the ignored ones, each
+    in annotation order (get_cls_results, mean_ap.py:270-294) -, gt_off int32 [S + 1], gt_reg int32 [S])"""
+    n, C = len(results), int(num_classes)
+    assert len(annotations) == n
+    S = n * C
+    flat = [np.reshape(r[c], (-1, 5)) for r in results for c in range(C)]
+    cnt = np.fromiter((len(a) for a in flat), dtype=np.int64, count=S)
+    dets = np.concatenate(flat).astype(np.float32, copy=False) if S else np.zeros((0, 5), np.float32)
+    boxes, labels, imgs, ign = [], [], [], []
+    for which, (bk, lk) in enumerate((('bboxes', 'labels'), ('bboxes_ignore', 'labels_ignore'))):
+        anns = annotations if which == 0 else [a if a.get('labels_ignore', None) is not None else {} for a in annotations]
+        b = [np.reshape(a.get(bk, ()), (-1, 4)) for a in anns]
+        k = np.fromiter((len(x) for x in b), dtype=np.int64, count=n)
+        boxes += b
+        labels += [np.reshape(a.get(lk, ()), (-1,)) for a in anns]
+        imgs.append(np.repeat(np.arange(n, dtype=np.int64), k))
+        ign.append(np.full(int(k.sum()), which, dtype=np.int64))
+    boxes = np.concatenate(boxes).astype(np.float32, copy=False) if n else np.zeros((0, 4), np.float32)
+    labels = np.concatenate(labels).astype(np.int64) if n else np.zeros(0, np.int64)
+    imgs, ign = np.concatenate(imgs), np.concatenate(ign)
+    keep = (labels >= 0) & (labels < C)
+    boxes, ign, seg = boxes[keep], ign[keep], (imgs * C + labels)[keep]
+    order = np.lexsort((ign, seg))               # (stable: by segment, regular before ignored, annotation order within)
+    assert dets.shape[0] < 2 ** 31 and boxes.shape[0] < 2 ** 31
+    off = lambda c: np.concatenate([[0], np.cumsum(c)]).astype(np.int32)           # noqa: E731
+    return dict(dets=np.ascontiguousarray(dets), det_off=off(cnt), gts=np.ascontiguousarray(boxes[order]),
+                gt_off=off(np.bincount(seg, minlength=S)), gt_reg=np.bincount(seg[ign == 0], minlength=S).astype(np.int32),
+                num_classes=C)
+
+
+def voc_flags_host(pack, iou_thrs, use_legacy_coordinate=False):
+    """``voc_flags`` over every segment of a pack: uint8 [n_thr, D]"""
+    dets, d_off, gts, g_off, g_reg = (pack[k] for k in ('dets', 'det_off', 'gts', 'gt_off', 'gt_reg'))
+    out = np.empty((len(iou_thrs), len(dets)), dtype=np.uint8)
+    for s in np.nonzero(np.diff(d_off))[0]:
+        d, g = dets[d_off[s]:d_off[s + 1]], gts[g_off[s]:g_off[s + 1]]
+        match = voc_match(d, g, use_legacy_coordinate)            # (once per segment, whatever the number of thresholds)
+        for t, thr in enumerate(iou_thrs):
+            out[t, d_off[s]:d_off[s + 1]] = voc_flags(d, g, g_reg[s], thr, use_legacy_coordinate, match)
+    return out
+
+
+def voc_flags_device(pack, iou_thrs, use_legacy_coordinate, device):
+    """the same flags from csrc/voc_eval.hip: one upload of the pack through the staging path, ONE launch for the split and
+    all thresholds, one download (``oadg_voc_tpfp.flags_device``, the module next to the package's import shim that holds the
+    ctypes call of the kernel; see its docstring for why that call is not in hip_ops.py)."""
+    import oadg_voc_tpfp
+    return oadg_voc_tpfp.flags_device(pack, iou_thrs, use_legacy_coordinate, device)
+
+
+def voc_accumulate(pack, flags, dataset=None):
+    """mean_ap.py:381-436 for one threshold (``flags`` uint8 [D] in pack order) -> (mean_ap, per_class): per class the
+    detections of all images by descending score (stable), fp32 cumulative tp / fp, recall over the REGULAR boxes, the AP
+    of the mode (``dataset='voc07'``: 11 points), and the mean over the classes that have a regular box (0.0 without any)"""
+    C, dets = pack['num_classes'], pack['dets']
+    det_cls = np.repeat(np.arange(len(pack['det_off']) - 1, dtype=np.int64) % C, np.diff(pack['det_off']))
+    reg_cls = np.bincount(np.arange(len(pack['gt_reg'])) % C, weights=pack['gt_reg'], minlength=C).astype(int)
+    mode = 'area' if dataset != 'voc07' else '11points'
+    eps = np.finfo(np.float32).eps
+    per_class = []
+    for c in range(C):
+        idx = np.nonzero(det_cls == c)[0]
+        num_gts = np.zeros(1, dtype=int)
+        num_gts[0] = reg_cls[c]
+        sort_inds = np.argsort(-dets[idx, 4], kind='stable')
+        f = flags[idx][sort_inds]
+        tp = np.cumsum((f == FLAG_TP).astype(np.float32)[None, :], axis=1)
+        fp = np.cumsum((f == FLAG_FP).astype(np.float32)[None, :], axis=1)
+        recalls = (tp / np.maximum(num_gts[:, np.newaxis], eps))[0, :]
+        precisions = (tp / np.maximum((tp + fp), eps))[0, :]
+        ap = np.float32(average_precision(recalls, precisions, mode))
+        per_class.append(dict(num_gts=num_gts.item(), num_dets=len(idx), recall=recalls, precision=precisions, ap=ap))
+    aps = [r['ap'] for r in per_class if r['num_gts'] > 0]
+    return (np.array(aps).mean().item() if aps else 0.0), per_class
+
+
+def eval_map_voc_thrs(results, annotations, num_classes, iou_thrs, dataset=None, use_legacy_coordinate=False, device=None):
+    """``eval_map_voc`` for several thresholds from ONE pack (and, with a device, one launch): a list of (mean_ap, per_class)"""
+    iou_thrs = [float(t) for t in iou_thrs]
+    pack = pack_voc_segments(results, annotations, num_classes)
+    out = []
+    for k in range(0, len(iou_thrs), VOC_MAX_THRS):
+        thrs = iou_thrs[k:k + VOC_MAX_THRS]
+        if device is None:
+            flags = voc_flags_host(pack, thrs, use_legacy_coordinate)
+        else:
+            flags = voc_flags_device(pack, thrs, use_legacy_coordinate, device)
+        out += [voc_accumulate(pack, flags[t], dataset) for t in range(len(thrs))]
+    return out
+
+
+def eval_map_voc(results, annotations, num_classes, iou_thr=0.5, dataset=None, use_legacy_coordinate=False, device=None):
+    """mean_ap.py:297-440 ``eval_map`` (scale_ranges=None, tpfp_default): (mean_ap, per_class) with per class
+    dict(num_gts, num_dets, recall, precision, ap).  results: per image, per class, [k, 5]; annotations: per image the
+    ``get_ann_info`` dict (bboxes, labels, and bboxes_ignore / labels_ignore when present).  ``dataset='voc07'``: 11-point AP.
+    ``device=None``: the host ``tpfp_default``; a torch device: csrc/voc_eval.hip - the same flags, so the same numbers."""
+    return eval_map_voc_thrs(results, annotations, num_classes, [iou_thr], dataset, use_legacy_coordinate, device)[0]
+
+
+def voc_device():
+    """the device ``SdgodDataset.evaluate`` matches on: the current GPU when the library and a GPU are present, else None
+    (the host path)"""
+    import torch
+    from . import _lib
+    if torch.cuda.is_available() and os.path.exists(_lib.LIB_PATH):
+        return torch.device('cuda', torch.cuda.current_device())
+    return None
+
+
+def sdgod_evaluate(ds, results, metric='mAP', logger=None, device='auto', **eval_kwargs):
+    """sdgod.py:29-89 for 'mAP': ``eval_map_voc`` with the legacy coordinates and, for a VOC2007 prefix, the 11-point AP,
+    per threshold -> the flat ordered dict (``AP50``, ..., ``mAP``).  'recall' / scale_ranges are rejected by name."""
+    metrics = list(metric) if isinstance(metric, (list, tuple)) else [metric]
+    check_evaluate_args(type(ds), metrics, eval_kwargs)
+    assert len(metrics) == 1, 'one metric (sdgod.py:56-58)'
+    assert len(results) == len(ds), f'{len(results)} results for {len(ds)} images'
+    thr = eval_kwargs.get('iou_thr', 0.5)
+    thrs = [thr] if isinstance(thr, float) else list(thr)
+    anns = [ds.get_ann_info(i) for i in range(len(ds))]
+    dev = voc_device() if device == 'auto' else device
+    per_thr = eval_map_voc_thrs(results, anns, _num_classes(ds), thrs, 'voc07' if ds.year == 2007 else None, True, dev)
+    out = {}
+    for t, (mean_ap, _) in zip(thrs, per_thr):
+        out[f'AP{int(t * 100):02d}'] = round(mean_ap, 3)
+    out['mAP'] = sum(m for m, _ in per_thr) / len(per_thr)
+    return out
+
+
 def evaluate(results, ds, metrics, num_classes, mmdet_style=False):
     """{'bbox': {AP, AP50, ...}} (COCO style) and / or {'mAP': ...} (VOC style AP@0.5).  ``mmdet_style``: the numbers and
     names of CocoDataset.evaluate (maxDets 100 / 300 / 1000, mAP at 1000 detections: mAP, mAP_50, ..., AR@100, ...) -
@@ -275,8 +494,8 @@ def _num_classes(ds):
 
 def dataset_evaluate(ds, results, metric='bbox', logger=None, **eval_kwargs):
     """``CocoDataset.evaluate`` (mmdet/datasets/coco.py:364-573, which CityscapesDataset delegates 'bbox' to) and
-    ``VOCDataset`` / ``SdgodDataset.evaluate`` (voc.py:28-106, sdgod.py:29-106) on this module's evaluators: the flat
-    ordered dict the reference returns.
+    ``VOCDataset.evaluate`` (voc.py:28-106) on this module's evaluators: the flat ordered dict the reference returns
+    (``SdgodDataset.evaluate`` is ``sdgod_evaluate`` above).
 
     'bbox': ``bbox_mAP, bbox_mAP_50, bbox_mAP_75, bbox_mAP_s, bbox_mAP_m, bbox_mAP_l`` as floats of 3 decimals (or the
     ``metric_items`` asked for) and ``bbox_mAP_copypaste`` - the mmdet-style numbers: maxDets = ``proposal_nums`` =
