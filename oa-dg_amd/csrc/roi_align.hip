@@ -843,8 +843,9 @@ int oadg_roi_align_fwd(const void* const* feats, const int* heights, const int* 
                        const float* scales, int levels, int N, int C, int dtype, float finest_scale,
                        const float* rois, int K, int PH, int PW, int sampling_ratio, int aligned,
                        void* out, const int* order, void* stream) {
-    if (!feats || !heights || !widths || !scales || !rois || !out) return OADG_EARG;
+    if (!feats || !heights || !widths || !scales) return OADG_EARG;
     if (K < 0 || PH < 1 || PW < 1 || (dtype != 0 && dtype != 1)) return OADG_EARG;
+    if (K > 0 && (!rois || !out)) return OADG_EARG;         // (no RoIs: the empty tensors' pointers are NULL)
     Pyramid p;
     const int rc = fill_pyramid(p, feats, nullptr, heights, widths, scales, levels, N, C, finest_scale);
     if (rc) return rc;
@@ -896,8 +897,9 @@ int oadg_roi_align_bwd(float* const* dfeats, const int* heights, const int* widt
                        int levels, int N, int C, int dtype, float finest_scale, const float* rois, int K,
                        int PH, int PW, int sampling_ratio, int aligned, const void* grad_out,
                        const int* order, void* stream) {
-    if (!dfeats || !heights || !widths || !scales || !rois || !grad_out) return OADG_EARG;
+    if (!dfeats || !heights || !widths || !scales) return OADG_EARG;
     if (K < 0 || PH < 1 || PW < 1 || (dtype != 0 && dtype != 1)) return OADG_EARG;
+    if (K > 0 && (!rois || !grad_out)) return OADG_EARG;    // (no RoIs: nothing to add, the maps stay as the caller zeroed them)
     Pyramid p;
     const int rc = fill_pyramid(p, nullptr, dfeats, heights, widths, scales, levels, N, C, finest_scale);
     if (rc) return rc;

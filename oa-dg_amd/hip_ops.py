@@ -498,14 +498,16 @@ class _RoIAlignFPN(torch.autograd.Function):
                 keys = torch.empty((K,), dtype=torch.int64, device=rois.device)
                 check(L.oadg_roi_order_keys(ptr(rois), K, N, len(feats), float(finest_scale), ptr(keys), stream_ptr()),
                       'oadg_roi_order_keys')
+            # (stable sorts: RoIs of one cell keep their index order, as in oadg_roi_order - the tile backward's summation
+            #  order is then fixed by contract above 8192 RoIs too)
             if keys is None:
                 pass
             elif tiles:     # the tile-gather backward walks the RoIs of one (level, image) group: group boundaries
-                skeys, order = keys.sort()
+                skeys, order = keys.sort(stable=True)
                 order = order.int()
                 rng_ = torch.searchsorted(skeys, _group_keys(len(feats), N, rois.device), out_int32=True)
             else:
-                order = keys.argsort().int()
+                order = keys.argsort(stable=True).int()
         check(_timed('roi_align_fwd', L.oadg_roi_align_fwd, P, Hs, Ws, Ss, len(feats), N, C,
                      0 if dt == torch.float32 else 1, float(finest_scale), ptr(rois), K, PH, PW,
                      int(sampling_ratio), int(bool(aligned)), ptr(out), ptr(order), stream_ptr()), 'oadg_roi_align_fwd')

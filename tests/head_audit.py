@@ -24,6 +24,15 @@ RHO = 2.0 ** -8          # one bf16 rounding
 # tests/test_head_audit.py with fp32 maps: roi_align_bwd_kernel and roi_align_fwd_rows_kernel<float>) is 0.061, a margin of
 # 16x.  (The bf16 outputs of the audited steps reach 0.87 - 0.98: one bf16 rounding of a value just above a power of two,
 # the RHO term, not this one.)
+# Away from 7 x 7 / adaptive / aligned (tests/test_roi_align_stress.py: pooled sides 1 .. 14, sampling ratios 1 - 3, unaligned
+# RoIs, bins of 31 - 97 pixels on both sides of the table overflows, 4 - 516 channels, maps down to 1 x 1, 2 - 8 tiles per
+# workgroup, degenerate boxes, more than 8192 RoIs) the same constants hold on the MI355X with no RoI taking the other side of
+# a borderline choice - worst err / bound of the fp32 outputs:
+#   roi_align_bwd_kernel 0.089 (97-pixel bins, 194 samples per bin through roi_bwd_scatter; 0.065 for two-sample bins 70
+#   pixels wide, at most 0.004 in every other family), roi_align_fwd_rows_kernel<float> 0.040 (two-sample bins of 20 - 70
+#   pixels; 0.007 elsewhere); with 33 x 33 samples per bin both stay below 0.025.
+# (bf16 outputs: roi_align_fwd_rows_kernel<unsigned short> 0.84, roi_align_bwd_tiles_kernel 0.79, roi_align_bwd_kernel with
+# bf16 maps - a pooled side above 8 - 0.57: RHO.)
 GAMMA_ROI = 2.0 ** -16
 # fp32 arithmetic of the loss kernels (logf / expf, per-element terms summed in fp64, the final fp32 scalings).  Set from
 # measurement: the worst err / bound of the fp32 outputs over the three audited steps is 0.072 (supcon's feature gradient,
@@ -278,14 +287,15 @@ def roi_order_expect(rois, n_img, levels, finest_scale):
     the level is borderline -, group of every candidate)"""
     r32 = rois.to(torch.float32)
     r = rois.to(torch.float64)
-    w, h = (r[:, 3] - r[:, 1]).clamp_min(0), (r[:, 4] - r[:, 2]).clamp_min(0)
+    # (a NaN coordinate: fmaxf(NaN, 0) is 0 - level 0 - and the conversion of a NaN cell coordinate to int gives 0)
+    w, h = torch.nan_to_num(r[:, 3] - r[:, 1], nan=0.0).clamp_min(0), torch.nan_to_num(r[:, 4] - r[:, 2], nan=0.0).clamp_min(0)
     v = torch.log2(torch.sqrt(w * h) / finest_scale + 1e-6)
     cands = []
     for shift in (0, 1, -1):
         lvl = torch.floor(v + shift * TOL_LVL).clamp(0, levels - 1).long()
         cell = (64.0 * (1 << lvl).to(torch.float32))
-        qx = (((r32[:, 1] + r32[:, 3]) * 0.5) / cell).trunc().long().clamp(0, 1023)
-        qy = (((r32[:, 2] + r32[:, 4]) * 0.5) / cell).trunc().long().clamp(0, 1023)
+        qx = torch.nan_to_num((((r32[:, 1] + r32[:, 3]) * 0.5) / cell).trunc(), nan=0.0).long().clamp(0, 1023)
+        qy = torch.nan_to_num((((r32[:, 2] + r32[:, 4]) * 0.5) / cell).trunc(), nan=0.0).long().clamp(0, 1023)
         b = r32[:, 0].trunc().long().clamp(0, n_img - 1)
         cands.append((((lvl * n_img + b) * 1024 + qy) * 1024 + qx, lvl * n_img + b))
     return cands
