@@ -388,13 +388,47 @@ int oadg_voc_tpfp(const float* dets, const int32_t* det_off, const float* gts, c
  *     oadg_png_encode_workspace_bytes(n, H, W) bytes; OADG_ESIZE when it is smaller.
  *   oadg_png_write_rgb8 (HOST function, no device work, takes no interpreter lock): signature, IHDR (8-bit, colour type 2,
  *     non-interlaced), IDAT chunk(s) holding the stream, IEND, each with its CRC-32; OADG_EIO when the file cannot be written.
- * Called from the offline tools (tools/analysis_tools/get_corrupted_dataset.py, tools/bench_png_encode.py) only. */
+ * Called from oadg_draw.py (PngEncoder: tools/analysis_tools/get_corrupted_dataset.py, --show-dir) and tools/bench_png_encode.py. */
 size_t oadg_png_encode_stream_capacity(int H, int W);
 int oadg_png_encode_segments(int H, int W);
 size_t oadg_png_encode_workspace_bytes(int n, int H, int W);
 int oadg_png_encode_rgb8(const uint8_t* imgs, int n, int H, int W, int bgr, int filter_mode, uint8_t* streams,
                          size_t capacity, int64_t* stream_bytes, void* workspace, size_t workspace_bytes, void* stream);
 int oadg_png_write_rgb8(const char* path, const uint8_t* zstream_host, size_t bytes, int H, int W);
+
+/* ------------------------------------------------------------------------------------------------
+ * Drawing detections: a display list painted in place on a resident batch (csrc/draw.hip)
+ *   replaces imshow_det_bboxes  mmdet/core/visualization/image.py:19-223 (matplotlib patches and text on the host) behind
+ *            BaseDetector.show_result and tools/test.py --show-dir
+ * imgs: uint8 [n][H][W][3], painted in place; a colour is 3 bytes packed b0 | b1 << 8 | b2 << 16 and b0 goes to the lowest
+ * address (channel meaning is the caller's).  items: int32 [n_items][OADG_DRAW_ITEM_INTS]; image i owns the rows
+ * item_off[i] .. item_off[i + 1] - 1 (item_off: int32 [n + 1]; clamped to [0, n_items] by the kernel).  A row is
+ *   { OADG_DRAW_OUTLINE, x0, y0, x1, y1, w,     colour, 0 }   corners inclusive; pixel (x, y) of the box is painted iff
+ *                                                             x - x0 < w or x1 - x < w or y - y0 < w or y1 - y < w: the line
+ *                                                             grows inward, 2w >= a side fills, w <= 0 paints nothing
+ *   { OADG_DRAW_FILL,    x0, y0, x1, y1, 0,     colour, 0 }   corners inclusive
+ *   { OADG_DRAW_TEXT,    x,  y,  offset, length, scale, colour, 0 }   text[offset .. offset + length - 1] in the fixed
+ *                                                             6 x 11 font of csrc/font6x11.h: character c occupies columns
+ *                                                             x + 6 * scale * c .. + 6 * scale - 1 and rows y .. y + 11 * scale
+ *                                                             - 1, each glyph bit scale x scale pixels; only set bits
+ *                                                             paint; bytes outside 32 .. 126 paint nothing
+ * Painter's order: the result is that of applying the rows one after another (the last row that covers a pixel wins), the
+ * same bytes from run to run.  x1 < x0 or y1 < y0, an unknown kind, scale < 1 and a text run that does not lie inside
+ * [0, text_bytes) paint nothing (the kernel's own guard: oadg_draw.draw_items refuses such a run, and a negative offset or
+ * length, on the host before anything is uploaded); everything is clipped to the image; every coordinate, width and scale may be any int32.
+ * These are Pillow's ImageDraw.rectangle(outline=, width=), rectangle(fill=) and text() with its built-in bitmap font.
+ * Pixels nothing paints are neither read nor written.  text: uint8 [text_bytes] (may be NULL when text_bytes is 0;
+ * text_bytes < 2^31).  ceil(W / 64) * ceil(H / 16) * n < 2^31 (OADG_ESIZE otherwise).  One launch (none when n_items is 0).
+ * oadg_draw_tile_capacity: the rows a workgroup lists for its tile before it paints and starts the list over
+ * (= OADG_DRAW_TILE_CAPACITY; any number of rows may cover a tile).  Called from oadg_draw.py only. */
+#define OADG_DRAW_OUTLINE 0
+#define OADG_DRAW_FILL 1
+#define OADG_DRAW_TEXT 2
+#define OADG_DRAW_ITEM_INTS 8
+#define OADG_DRAW_TILE_CAPACITY 256
+int oadg_draw_tile_capacity(void);
+int oadg_draw_items_u8(uint8_t* imgs, int n, int H, int W, const int32_t* items, const int32_t* item_off, int n_items,
+                       const uint8_t* text, size_t text_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * JPEG input files (csrc/jpeg_decode.hip): entropy stage on the HOST, pixel stage on the DEVICE

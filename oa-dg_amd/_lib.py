@@ -76,6 +76,8 @@ OP_ENH_BRIGHTNESS, OP_ENH_COLOR, OP_ENH_CONTRAST, OP_ENH_SHARPNESS = 8, 9, 10, 1
 CORRUPT_NEAREST, CORRUPT_REFLECT, CORRUPT_MIRROR = 0, 1, 2
 CORRUPT_TO_U8_CLIP, CORRUPT_TO_U8, CORRUPT_TO_F32 = 0, 1, 2
 CORRUPT_BRIGHTNESS, CORRUPT_SATURATE = 0, 1
+DRAW_OUTLINE, DRAW_FILL, DRAW_TEXT = 0, 1, 2   # kinds of a display-list row (csrc/draw.hip)
+DRAW_ITEM_INTS = 8
 
 
 # ---- the tables that are filled with numpy: Structure + its record dtype (pointer fields come out as uint64) ----------------
@@ -253,6 +255,8 @@ SIGNATURES = {
     'oadg_png_encode_workspace_bytes': (cs, [ci, ci, ci]),
     'oadg_png_encode_rgb8': (ci, [vp, ci, ci, ci, ci, ci, vp, cs, vp, vp, cs, vp]),
     'oadg_png_write_rgb8': (ci, [c_char_p, vp, cs, ci, ci]),
+    'oadg_draw_tile_capacity': (ci, []),
+    'oadg_draw_items_u8': (ci, [vp, ci, ci, ci, vp, vp, ci, vp, cs, vp]),
     'oadg_jpeg_size': (ci, [c_char_p, POINTER(ci), POINTER(ci)]),
     'oadg_jpeg_coef_capacity': (cs, [ci, ci]),
     'oadg_jpeg_entropy_decode': (ci, [c_char_p, ci, ci, vp, cs, vp]),

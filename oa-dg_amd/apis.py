@@ -676,21 +676,95 @@ def parse_optimizer_config(cfg):
     return dict(grad_clip=clip)
 
 
-def single_gpu_test(model, dataset, pipe, amp, samples_per_gpu, max_samples=None, indices=None):
+def single_gpu_test(model, dataset, pipe, amp, samples_per_gpu, max_samples=None, indices=None, show_dir=None,
+                    show_score_thr=0.3):
     """apis/test.py:15-70 ``single_gpu_test``: ``model(return_loss=False, rescale=True, **data)`` over the dataset through
     the device test pipeline, ``samples_per_gpu`` images per forward pass; one ``list[np.ndarray [k, 5]]`` (per class) per
     image.  ``indices``: the images to test, in this order (a rank's shard); default: the first ``max_samples`` (all).
-    Runs on the current stream, draws no random number and leaves the model's mode alone (the caller's ``model.eval()``)."""
+    Runs on the current stream, draws no random number and leaves the model's mode alone (the caller's ``model.eval()``).
+    ``show_dir``: after its forward pass every batch is painted with its detections above ``show_score_thr`` - on a copy of
+    the uint8 images the network was fed (the corrupted ones behind a ``Corrupt`` step) - and written as
+    ``<show_dir>/<ori_filename, extension .png>`` (``<index:06d>.png`` for a dataset without files): painted and encoded on
+    the device, written by threads (visualization.ShowWriter).  The results are those of a run without it."""
     if indices is None:
         indices = range(len(dataset) if max_samples is None else min(len(dataset), max_samples))
     indices = list(indices)
-    results = []
-    for i in range(0, len(indices), samples_per_gpu):
-        imgs, boxes, labels = dataset.batch(indices[i:i + samples_per_gpu])
-        data = pipe.test_batch(imgs)
-        with torch.no_grad(), torch.autocast('cuda', dtype=amp, enabled=amp is not None):
-            results.extend(model(return_loss=False, rescale=True, **data))
+    results, writer = [], None
+    if show_dir is not None:
+        from . import visualization
+        writer = visualization.ShowWriter(show_dir, dataset, next(model.parameters()).device, score_thr=show_score_thr)
+    try:
+        for i in range(0, len(indices), samples_per_gpu):
+            chunk = indices[i:i + samples_per_gpu]
+            imgs, boxes, labels = dataset.batch(chunk)
+            data, fed = pipe.test_batch(imgs, return_fed=True) if writer is not None else (pipe.test_batch(imgs), None)
+            with torch.no_grad(), torch.autocast('cuda', dtype=amp, enabled=amp is not None):
+                batch_results = model(return_loss=False, rescale=True, **data)
+            results.extend(batch_results)
+            if writer is not None:
+                writer.add(fed, batch_results, chunk)
+    except BaseException:
+        if writer is not None:
+            writer.abort()                       # (stop the threads; what the loop raised is what the caller sees)
+        raise
+    if writer is not None:
+        writer.close()
     return results
+
+
+def init_detector(config, checkpoint=None, device='cuda:0', cfg_options=None, amp='bf16'):
+    """apis/inference.py:19-58 ``init_detector``: a detector built from ``config`` (a path or a Config), ``checkpoint``
+    loaded into it (None or 'none': the initial weights), on ``device`` in eval mode, with ``model.cfg`` set and
+    ``model.CLASSES`` from the checkpoint's meta or the test split's dataset class.  ``amp``: 'bf16' (what tools/test.py
+    tests with; switches the bf16 convolutions on) or None."""
+    from . import hip_conv
+    from .config import Config
+    from .registry import DATASETS, build_detector
+    cfg = Config.fromfile(config) if isinstance(config, (str, os.PathLike)) else config
+    if cfg_options:
+        cfg.merge_from_dict(cfg_options)
+    cfg.model.pop('pretrained', None)
+    model = build_detector(cfg.model, test_cfg=cfg.get('test_cfg'))
+    classes = None
+    if checkpoint is not None and checkpoint != 'none':
+        from .checkpoint import load_checkpoint
+        rep = load_checkpoint(model, checkpoint, map_location='cpu', strict=False, logger=None)
+        lost = rep['missing'] + [m[0] for m in rep['mismatched']]
+        if lost:
+            raise RuntimeError(f'{len(lost)} model tensors are not provided by {checkpoint} (e.g. {lost[:4]})')
+        classes = (rep.get('meta') or {}).get('CLASSES')
+    else:
+        model.init_weights(allow_missing_pretrained=True)
+    test = cfg.data.test[0] if isinstance(cfg.data.test, (list, tuple)) else cfg.data.test
+    if classes is None:
+        classes = test.get('classes') or getattr(DATASETS.get(test['type']), 'CLASSES', None)
+    model.cfg, model.CLASSES = cfg, classes
+    model.amp = torch.bfloat16 if amp == 'bf16' else None
+    model = model.to(torch.device(device)).to(memory_format=torch.channels_last).eval()
+    if model.amp is not None:
+        hip_conv.enable()
+    return model
+
+
+def inference_detector(model, imgs):
+    """apis/inference.py:88-160 ``inference_detector``: ``imgs`` - a path, a uint8 [H, W, 3] (B, G, R) array, or a list /
+    tuple of those - through the test pipeline of ``model.cfg`` (pipelines.DevicePipeline.test_batch) and the detector;
+    one image's result, or a list of them for a list.  Files are decoded as the datasets decode them (colour, B, G, R)."""
+    from .pipelines import DevicePipeline
+    from .visualization import resident_image
+    is_batch = isinstance(imgs, (list, tuple))
+    device = next(model.parameters()).device
+    test = model.cfg.data.test[0] if isinstance(model.cfg.data.test, (list, tuple)) else model.cfg.data.test
+    pipe = getattr(model, '_inference_pipe', None)
+    if pipe is None:
+        pipe = model._inference_pipe = DevicePipeline(test['pipeline'], dtype=model.amp or torch.float32)
+    results = []
+    with torch.cuda.device(device):
+        for img in (imgs if is_batch else [imgs]):
+            data = pipe.test_batch(resident_image(img, device))
+            with torch.no_grad(), torch.autocast('cuda', dtype=model.amp, enabled=model.amp is not None):
+                results.extend(model(return_loss=False, rescale=True, **data))
+    return results if is_batch else results[0]
 
 
 def shard_indices(n, rank, world):

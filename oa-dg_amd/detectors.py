@@ -161,6 +161,26 @@ class BaseDetector(nn.Module):
         assert 'proposals' not in kwargs
         return self.aug_test(imgs, img_metas, **kwargs)
 
+    def show_result(self, img, result, score_thr=0.3, bbox_color=(72, 101, 241), text_color=(72, 101, 241), mask_color=None,
+                    thickness=2, font_size=13, win_name='', show=False, wait_time=0, out_file=None):
+        """base.py:472-561: draw ``result`` (one image's per-class list, or ``(bbox_result, segm_result)``) over a copy of
+        ``img`` - a path, a uint8 [H, W, 3] BGR array or a resident tensor - on the device (visualization.py,
+        csrc/draw.hip).  Writes a PNG when ``out_file`` is given, returns the drawn BGR numpy image when it is not."""
+        if show:
+            raise NotImplementedError("show_result(show=True) is not built: there is no window here; pass out_file=... or "
+                                      "take the returned image")
+        if mask_color is not None:
+            raise NotImplementedError(f'show_result(mask_color={mask_color!r}) is not built: the detectors here have no '
+                                      f'mask branch')
+        if isinstance(result, tuple):
+            result = result[0]
+        from . import visualization
+        param = next(self.parameters(), None)
+        device = param.device if param is not None and param.is_cuda else torch.device('cuda', torch.cuda.current_device())
+        return visualization.show_result(img, result, getattr(self, 'CLASSES', None), device, score_thr=score_thr,
+                                         out_file=out_file, bbox_color=bbox_color, text_color=text_color,
+                                         thickness=thickness, font_size=font_size)
+
     def _parse_losses(self, losses):
         """base.py:234-277.  Same keys and values; the per-variable all-reduces + .item() of the reference
         become one packed all-reduce and one host read."""

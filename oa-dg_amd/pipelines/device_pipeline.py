@@ -137,12 +137,14 @@ class DevicePipeline:
         self.dtype = dtype
 
     @torch.no_grad()
-    def test_batch(self, imgs_u8):
+    def test_batch(self, imgs_u8, return_fed=False):
         """The reference's test pipeline ([Corrupt,] MultiScaleFlipAug(img_scale, flip)[Resize(keep_ratio), RandomFlip,
         Normalize, Pad, ImageToTensor, Collect]) for a resident uint8 batch: returns ``dict(img=[tensor, ...],
         img_metas=[[meta, ...], ...])`` as ``forward_test`` expects - one entry per test-time augmentation, scales outer,
         (no flip, then one flip per direction) inner (test_time_aug.py:99-121).  A ``Corrupt`` step in front of it
-        (tools/analysis_tools/test_robustness.py --load-dataset original) corrupts the uint8 images first."""
+        (tools/analysis_tools/test_robustness.py --load-dataset original) corrupts the uint8 images first.
+        ``return_fed``: return ``(that dict, the uint8 batch the network was fed before Resize and Normalize)`` - the
+        corrupted images when there is a ``Corrupt`` step, else ``imgs_u8`` itself (``--show-dir`` draws on a copy of it)."""
         assert self.test_aug is not None, 'test_batch needs a test pipeline (MultiScaleFlipAug)'
         L = _lib.lib()
         if self.corrupt is not None:
@@ -187,7 +189,8 @@ class DevicePipeline:
                     metas[i].update(img_shape=(H, W, 3), pad_shape=(Hp, Wp, 3))
                 out_imgs.append(img)
                 out_metas.append(metas)
-        return dict(img=out_imgs, img_metas=out_metas)
+        data = dict(img=out_imgs, img_metas=out_metas)
+        return (data, imgs_u8) if return_fed else data
 
     def prefetch(self, imgs_u8, gt_bboxes, gt_labels, worker_seed=None, ready=None):
         """Enqueue the whole pipeline for one batch on a side stream and return a handle (``.get()``).

@@ -20,9 +20,9 @@ DEVICE_CORRUPTIONS, the host transform for the rest), then csrc/png_encode.hip t
 wraps them into files on up to ``--workers`` threads (at most 16; the call takes no interpreter lock).  Encoding, the copy
 and the writes of one batch run while the next one is corrupted.
 
-The tool needs the GPU: like every other device path of this project it has no host fallback.  (Its C-ABI calls live here,
-not in the package: it is an offline tool, no training or inference step calls them - as
-tools/dataset_converters/cityscapes.py does.)
+The tool needs the GPU: like every other device path of this project it has no host fallback.  (``PngEncoder`` and
+``write_png`` - the C-ABI calls - live in oadg_draw.py next to the package's import shim, which the test loop's
+``--show-dir`` uses too; they are importable from here under the same names.)
 """
 import argparse
 import copy
@@ -35,10 +35,11 @@ from concurrent.futures import ThreadPoolExecutor
 ROOT = osp.dirname(osp.dirname(osp.dirname(osp.abspath(__file__))))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+# the device PNG encoder (csrc/png_encode.hip) and the file writer, re-exported under the names they had here; the test
+# loop's --show-dir uses them too.  (Imports torch and the package: the library itself is loaded at first use.)
+from oadg_draw import BATCH, PINNED_SLOTS, PngEncoder, write_png  # noqa: E402,F401
 
 MAX_THREADS = 16
-BATCH = 8                    # images per encode (8 x 1024 x 2048 x 3 bytes in, at most 8 x 6.4 MB of pinned memory out)
-PINNED_SLOTS = 3             # one being filled by the device, one being written, one spare
 CHOICES = ['all', 'benchmark', 'noise', 'blur', 'weather', 'digital', 'holdout', 'None', 'gaussian_noise', 'shot_noise',
            'impulse_noise', 'defocus_blur', 'glass_blur', 'motion_blur', 'zoom_blur', 'snow', 'frost', 'fog', 'brightness',
            'contrast', 'elastic_transform', 'pixelate', 'jpeg_compression', 'speckle_noise', 'gaussian_blur', 'spatter',
@@ -94,77 +95,6 @@ def writer_threads(workers, debug=False):
 
 
 # ------------------------------------------------------------------------------------------------------ device path
-class PngEncoder:
-    """csrc/png_encode.hip on resident uint8 [n, H, W, 3] batches: ``launch`` enqueues the encode and the copy of the
-    streams into a pinned slot on the current stream, ``finish`` waits for that copy and returns per image (address, bytes)
-    of its stream in the slot.  A slot is handed out again only after ``release`` (its files are written)."""
-
-    def __init__(self, device, slots=PINNED_SLOTS, filter_mode=-1):
-        import torch
-        from oadg_amd import _lib
-        self.torch, self._lib, self.L, self.device = torch, _lib, _lib.lib(), torch.device(device)
-        self.filter_mode, self.device_ms, self.images = filter_mode, 0.0, 0
-        self._slots = [dict(host=None, sizes=None, busy=[]) for _ in range(slots)]
-        self._next = 0
-
-    def launch(self, imgs, bgr=True):
-        torch, L, _lib = self.torch, self.L, self._lib
-        n, H, W, _ = imgs.shape
-        cap = int(L.oadg_png_encode_stream_capacity(H, W))
-        ws_bytes = int(L.oadg_png_encode_workspace_bytes(n, H, W))
-        if cap == 0 or ws_bytes == 0:
-            raise ValueError(f'a batch of {n} images of {H} x {W}: (3W + 1) * H must stay below 2^31')
-        slot = self._slots[self._next]
-        self._next = (self._next + 1) % len(self._slots)
-        for f in slot['busy']:                                     # the writes that still read this slot
-            f.result()
-        slot['busy'] = []
-        if slot['host'] is None or slot['host'].numel() < n * cap:
-            slot['host'] = torch.empty((n * cap,), dtype=torch.uint8, pin_memory=True)
-        if slot['sizes'] is None or slot['sizes'].numel() < n:
-            slot['sizes'] = torch.empty((max(n, BATCH),), dtype=torch.int64, pin_memory=True)
-        imgs = imgs.contiguous()
-        streams = torch.empty((n * cap,), dtype=torch.uint8, device=self.device)
-        sizes = torch.empty((n,), dtype=torch.int64, device=self.device)
-        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=self.device)
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        _lib.check(L.oadg_png_encode_rgb8(_lib.ptr(imgs), n, H, W, int(bool(bgr)), self.filter_mode, _lib.ptr(streams), cap,
-                                          _lib.ptr(sizes), _lib.ptr(ws), ws_bytes, _lib.stream_ptr()), 'oadg_png_encode_rgb8')
-        t1.record()
-        slot['host'][:n * cap].copy_(streams, non_blocking=True)
-        slot['sizes'][:n].copy_(sizes, non_blocking=True)
-        done = torch.cuda.Event()
-        done.record()
-        return dict(slot=slot, n=n, H=H, W=W, cap=cap, t0=t0, t1=t1, done=done, keep=(imgs, streams, sizes, ws))
-
-    def finish(self, job):
-        """-> [(host address, bytes)] per image, valid until the slot's release()"""
-        job['done'].synchronize()
-        self.device_ms += job['t0'].elapsed_time(job['t1'])
-        self.images += job['n']
-        job['keep'] = None
-        sizes = job['slot']['sizes'][:job['n']].tolist()
-        if max(sizes) > job['cap']:
-            raise RuntimeError(f'oadg_png_encode_rgb8 needs {max(sizes)} bytes, above its own bound {job["cap"]}')
-        base = job['slot']['host'].data_ptr()
-        return [(base + i * job['cap'], int(b)) for i, b in enumerate(sizes)]
-
-    @staticmethod
-    def release(job, futures):
-        """the slot of ``job`` is reused once ``futures`` (the writes that read it) are done"""
-        job['slot']['busy'] = list(futures)
-
-
-def write_png(L, path, address, nbytes, H, W):
-    rc = L.oadg_png_write_rgb8(path.encode(), address, nbytes, H, W)
-    if rc == -3:
-        raise OSError(f'{path}: cannot be written')
-    if rc != 0:
-        raise RuntimeError(f'{path}: oadg_png_write_rgb8 failed with {rc}')
-    return nbytes
-
-
 def resident_split(ds):
     """the decoded split on the device: [(dataset indices, uint8 [n, H, W, 3] as the loader yields it: B, G, R)] - consecutive
     images of one extent form batches of at most BATCH"""

@@ -4,6 +4,8 @@ apis/test.py): CONFIG CHECKPOINT [--out results.pkl] [--eval bbox] [--cfg-option
 
 Runs ``model(return_loss=False, rescale=True, **data)`` over the test split through the device test pipeline and
 collects one ``list[np.ndarray [k, 5]]`` (per class) per image, the format ``--out`` pickles in the reference.
+``--show-dir DIR [--show-score-thr T]`` also writes every tested image with its detections painted on it
+(oadg_amd/visualization.py: painted and PNG-encoded on the device, ``DIR/<ori_filename>.png``).
 ``--eval bbox`` reports the COCO-style numbers the reference's Cityscapes / COCO datasets report (AP@[.50:.95], AP50,
 AP75, APs/m/l, AR...: oadg_amd/evaluation.py, a restatement of pycocotools' COCOeval, which this image does not have);
 ``--eval mAP`` the VOC-style AP@0.5 of mmdet/core/evaluation/mean_ap.py ``eval_map`` (area mode).
@@ -35,9 +37,24 @@ def parse_args():
     p.add_argument('--amp', default='bf16', choices=['bf16', 'none'])
     p.add_argument('--allow-partial-checkpoint', action='store_true',
                    help='evaluate even if the checkpoint lacks (or mis-sizes) some model tensors')
+    add_show_arguments(p)
     a = p.parse_args()
     os.environ.setdefault('LOCAL_RANK', str(a.local_rank))
+    check_show_arguments(a)
     return a
+
+
+def add_show_arguments(p):
+    """tools/test.py:52-60 of the reference: --show, --show-dir, --show-score-thr"""
+    p.add_argument('--show', action='store_true', help='show results in a window (not built: use --show-dir)')
+    p.add_argument('--show-dir', help='directory where the painted images will be saved (PNG, painted and encoded on the device)')
+    p.add_argument('--show-score-thr', type=float, default=0.3, help='score threshold of the painted detections (default: 0.3)')
+
+
+def check_show_arguments(a):
+    if a.show:
+        raise NotImplementedError('--show (a window per image) is not built: there is no display here; --show-dir DIR '
+                                  'writes the painted images instead')
 
 
 def build_model(cfg, checkpoint, dev, amp, allow_partial=False):
@@ -63,7 +80,7 @@ def build_model(cfg, checkpoint, dev, amp, allow_partial=False):
     return model
 
 
-def run_test(model, data_cfg, dev, amp, samples_per_gpu=1, max_samples=None):
+def run_test(model, data_cfg, dev, amp, samples_per_gpu=1, max_samples=None, show_dir=None, show_score_thr=0.3):
     """single_gpu_test (apis/test.py:15-70) over one test-split config: (results, dataset, seconds)"""
     from oadg_amd.apis import single_gpu_test
     from oadg_amd.datasets import build_dataset
@@ -71,7 +88,8 @@ def run_test(model, data_cfg, dev, amp, samples_per_gpu=1, max_samples=None):
     ds = build_dataset(data_cfg, default_args=dict(seed=12345, device=dev, test_mode=True), synthetic_fallback=True)
     pipe = DevicePipeline(data_cfg['pipeline'], dtype=amp or torch.float32)
     t0 = time.time()
-    results = single_gpu_test(model, ds, pipe, amp, samples_per_gpu, max_samples)
+    results = single_gpu_test(model, ds, pipe, amp, samples_per_gpu, max_samples, show_dir=show_dir,
+                              show_score_thr=show_score_thr)
     torch.cuda.synchronize()
     return results, ds, time.time() - t0
 
@@ -87,7 +105,8 @@ def main():
     amp = torch.bfloat16 if a.amp == 'bf16' else None
     model = build_model(cfg, a.checkpoint, dev, amp, a.allow_partial_checkpoint)
     dcfg = cfg.data.test
-    results, ds, dt = run_test(model, dcfg, dev, amp, cfg.data.get('samples_per_gpu', 1), a.max_samples)
+    results, ds, dt = run_test(model, dcfg, dev, amp, cfg.data.get('samples_per_gpu', 1), a.max_samples,
+                               show_dir=a.show_dir, show_score_thr=a.show_score_thr)
     n = len(results)
     print(f'{n} images in {dt:.2f} s ({n / dt:.1f} img/s), {sum(len(c) for r in results for c in r)} detections')
     if a.out:
