@@ -371,6 +371,38 @@ int oadg_voc_tpfp(const float* dets, const int32_t* det_off, const float* gts, c
                   int32_t* iou_arg, uint8_t* flags, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * COCO-protocol evaluation: the greedy matching of a whole test split (csrc/coco_eval.hip)
+ *   replaces COCOeval.evaluateImg  pycocotools/cocoeval.py (one Python problem per image, category and area range, a triple
+ *            loop over thresholds x detections x ground truth) and maskUtils.iou on boxes, as evaluation._evaluate_img and
+ *            _iou_xywh restate them
+ * A segment is one (image, category) pair, n_seg of them.  dets: fp64 [n_det][4] = x, y, w, h, concatenated in segment order,
+ * within a segment by descending score (stable) and already cut to the largest maxDets; det_off: int32 [n_seg + 1]; gts: fp64
+ * [n_gt][4] = x, y, w, h, within a segment in annotation order; gt_area: fp64 [n_gt], the annotation's area field; gt_crowd:
+ * uint8 [n_gt]; gt_off: int32 [n_seg + 1].  Offsets are clamped to the arrays' extents before use.
+ * iou_thrs_host: n_thr thresholds, area_rng_host: n_area pairs lo, hi (both inclusive), in HOST memory (read during the call);
+ * n_thr * n_area <= OADG_COCO_MAX_LANES.  A box is ignored in range r iff crowd || area < lo || area > hi.
+ * Per (range r, threshold t) the detections of a segment are visited in order; each takes, among the boxes not yet taken
+ * (a crowd is never taken) whose fp64 IoU - intersection / union, intersection / the detection's area for a crowd, 0 where that
+ * denominator is not positive; the host's operation order, no contraction, correctly rounded - is >= the running best
+ * (starting at the threshold), the LAST such non-ignored box in annotation order, or without one the last such ignored box.
+ *   flags [n_area][n_thr][n_det] uint8: 0 = unmatched and w * h of the detection inside the range (a false positive), 1 =
+ *     matched to a non-ignored box (a true positive), 2 = ignored: matched to an ignored box, or unmatched and w * h outside.
+ *   match [n_area][n_thr][n_det] int32, may be NULL (then not written): the matched box's index within its segment, or -1.
+ * Every element that belongs to a detection of a segment is written; the same bytes from run to run.  Segments of up to
+ * OADG_COCO_LDS_GTS boxes are staged once; larger ones in chunks of that size, detections OADG_COCO_LDS_DETS at a time.
+ * The workspace (8-byte aligned) must hold oadg_coco_match_workspace_bytes(...) bytes (0: arguments the call refuses);
+ * OADG_ESIZE when it is smaller.  One launch for the split, all thresholds and all ranges.  Called from oadg_coco_match.py only
+ * (the device half of evaluation.coco_eval_bbox(device=...)). */
+#define OADG_COCO_MAX_LANES 64
+#define OADG_COCO_LDS_GTS 128
+#define OADG_COCO_LDS_DETS 64
+size_t oadg_coco_match_workspace_bytes(int n_seg, int n_det, int n_gt, int n_thr, int n_area);
+int oadg_coco_match(const double* dets, const int32_t* det_off, const double* gts, const double* gt_area,
+                    const uint8_t* gt_crowd, const int32_t* gt_off, int n_seg, int n_det, int n_gt,
+                    const double* iou_thrs_host, int n_thr, const double* area_rng_host, int n_area, uint8_t* flags,
+                    int32_t* match, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * PNG output: a resident batch -> the zlib stream of every image, and the stream -> a file (csrc/png_encode.hip)
  *   replaces save_data  tools/analysis_tools/get_corrupted_dataset.py:83-113 (PIL.Image.fromarray(img).save(path): PNG row
  *            filtering and zlib deflate of every corrupted image on one host core)

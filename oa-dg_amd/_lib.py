@@ -64,6 +64,7 @@ ROI_SAMPLE_MAX_IMAGES = 8
 RPN_MAX_LEVELS = 8
 PARSE_LOSSES_MAX = 32
 VOC_MAX_THRS = 8
+COCO_MAX_LANES, COCO_LDS_GTS, COCO_LDS_DETS = 64, 128, 64   # csrc/coco_eval.hip: matchings of one call, staging capacities
 
 
 class RegionOp(Structure):
@@ -250,6 +251,8 @@ SIGNATURES = {
     'oadg_instance_change_points': (ci, [vp, ci, ci, ci, ci, vp, ci, vp, vp, cs, vp]),
     'oadg_voc_tpfp_workspace_bytes': (cs, [ci, ci, ci, ci]),
     'oadg_voc_tpfp': (ci, [vp, vp, vp, vp, vp, ci, ci, ci, POINTER(cf), ci, ci, vp, vp, vp, vp, cs, vp]),
+    'oadg_coco_match_workspace_bytes': (cs, [ci, ci, ci, ci, ci]),
+    'oadg_coco_match': (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, POINTER(cd), ci, POINTER(cd), ci, vp, vp, vp, cs, vp]),
     'oadg_png_encode_stream_capacity': (cs, [ci, ci]),
     'oadg_png_encode_segments': (ci, [ci, ci]),
     'oadg_png_encode_workspace_bytes': (cs, [ci, ci, ci]),

@@ -81,16 +81,22 @@ def _evaluate_img(gts, dts, a_rng, max_det):
     return dict(dtm=dtm, dt_ig=dt_ig, g_ig=g_ig, scores=np.array([d['score'] for d in dts], np.float64))
 
 
-def coco_eval_bbox(gt_anns, results, num_classes, max_dets=None, names=None):
+def coco_eval_bbox(gt_anns, results, num_classes, max_dets=None, names=None, device=None):
     """gt_anns: per image, list of dict(bbox=[x, y, w, h], category=label index, area, iscrowd);
     results: per image, list over classes of arrays [k, 5] = x1, y1, x2, y2, score (``bbox2result`` format).
     Returns dict(metric name -> value) with the twelve COCO numbers (-1 where undefined).
     ``max_dets`` / ``names``: COCOeval's defaults (1, 10, 100) with its own names - what test_robustness.py's
     coco_eval_with_return reports - or MMDET_MAX_DETS / MMDET_METRICS for the numbers of ``CocoDataset.evaluate``
-    (tools/test.py --eval bbox)."""
+    (tools/test.py --eval bbox).
+    ``device=None``: the host loops below; a torch device: one pack, csrc/coco_eval.hip for the matching of the whole split,
+    a vectorised accumulate - the same flags, so the same twelve numbers (tests/test_hip_coco_eval.py compares with ==)."""
     MAX_DETS = list(max_dets) if max_dets is not None else [1, 10, 100]
     names = list(names) if names is not None else METRICS
     assert len(MAX_DETS) == 3 and len(names) == 12
+    if device is not None:
+        pack = pack_coco_segments(gt_anns, results, num_classes, MAX_DETS[-1])
+        precision, recall = coco_accumulate(pack, coco_flags_device(pack, IOU_THRS, AREA_RNG, device), MAX_DETS)
+        return coco_summarize(precision, recall, names)
     n_img = len(gt_anns)
     assert len(results) == n_img
     T, R, K, A, M = len(IOU_THRS), len(REC_THRS), num_classes, len(AREA_RNG), len(MAX_DETS)
@@ -141,6 +147,11 @@ def coco_eval_bbox(gt_anns, results, num_classes, max_dets=None, names=None):
                             q[ri] = pr[pi]
                     precision[t, :, k, a, m] = q
 
+    return coco_summarize(precision, recall, names)
+
+
+def coco_summarize(precision, recall, names=None):
+    """COCOeval.summarize: precision [T, R, K, A, M] and recall [T, K, A, M] (-1 where undefined) -> the twelve numbers"""
     def summarize(ap, iou=None, area=0, max_det=2):
         s = precision[:, :, :, area, max_det] if ap else recall[:, :, area, max_det]
         if iou is not None:
@@ -150,7 +161,137 @@ def coco_eval_bbox(gt_anns, results, num_classes, max_dets=None, names=None):
     stats = [summarize(1), summarize(1, .5), summarize(1, .75), summarize(1, None, 1), summarize(1, None, 2),
              summarize(1, None, 3), summarize(0, None, 0, 0), summarize(0, None, 0, 1), summarize(0, None, 0, 2),
              summarize(0, None, 1), summarize(0, None, 2), summarize(0, None, 3)]
-    return dict(zip(names, stats))
+    return dict(zip(METRICS if names is None else names, stats))
+
+
+# ------------------------------------------------------------------------------------------ COCO matching, one split at a time
+# The same protocol as ``coco_eval_bbox`` above cut into the steps of the device path: pack the split into flat arrays (one
+# segment per (image, category), as pack_voc_segments), match every segment for every (area range, threshold) - on the host
+# through ``_evaluate_img`` (the yardstick) or in one launch of csrc/coco_eval.hip -, accumulate with numpy.  All that
+# accumulate reads of the matching is one flag per (area range, threshold, detection).
+COCO_FP, COCO_TP, COCO_IGNORED = 0, 1, 2
+
+
+def pack_coco_segments(gt_anns, results, num_classes, max_det):
+    """a split as the arrays of oadg_coco_match: one segment per (image, category), s = image * num_classes + category.
+    dict(dets fp64 [D, 4] = x, y, w, h - per segment by descending score (stable) and cut to ``max_det`` -, det_off int32
+    [S + 1], gts fp64 [G, 4] = x, y, w, h in annotation order, gt_area fp64 [G] (the annotation's field), gt_crowd uint8 [G],
+    gt_off int32 [S + 1]; per kept detection det_score fp64, det_rank (its place within the segment) and det_cat; gt_cat)"""
+    n, K = len(gt_anns), int(num_classes)
+    assert len(results) == n
+    S = n * K
+    flat = [np.asarray(results[i][k], np.float64).reshape(-1, 5) for i in range(n) for k in range(K)]
+    cnt = np.fromiter((len(a) for a in flat), dtype=np.int64, count=S)
+    d = np.concatenate(flat) if S else np.zeros((0, 5), np.float64)
+    seg = np.repeat(np.arange(S, dtype=np.int64), cnt)
+    order = np.lexsort((-d[:, 4], seg))           # (stable: by segment, by descending score, by position among equal scores)
+    d = d[order]
+    first = np.concatenate([[0], np.cumsum(cnt)])
+    rank = np.arange(len(d), dtype=np.int64) - first[:-1][seg]
+    keep = rank < max_det
+    d, seg, rank = d[keep], seg[keep], rank[keep]
+    # CocoDataset._det2json / xyxy2xywh
+    dets = np.stack([d[:, 0], d[:, 1], d[:, 2] - d[:, 0], d[:, 3] - d[:, 1]], axis=1) if len(d) else np.zeros((0, 4))
+    anns = [(i, g) for i, per_img in enumerate(gt_anns) for g in per_img]
+    g_img = np.fromiter((i for i, _ in anns), dtype=np.int64, count=len(anns))
+    g_cat = np.fromiter((g['category'] for _, g in anns), dtype=np.int64, count=len(anns))
+    g_box = np.array([g['bbox'] for _, g in anns], np.float64).reshape(-1, 4)
+    g_area = np.fromiter((g['area'] for _, g in anns), dtype=np.float64, count=len(anns))
+    g_crowd = np.fromiter((bool(g['iscrowd']) for _, g in anns), dtype=np.uint8, count=len(anns))
+    ok = (g_cat >= 0) & (g_cat < K)
+    g_seg = (g_img * K + g_cat)[ok]
+    g_order = np.argsort(g_seg, kind='stable')     # (annotation order within a segment)
+    assert len(dets) < 2 ** 31 and len(g_order) < 2 ** 31
+    off = lambda c: np.concatenate([[0], np.cumsum(c)]).astype(np.int32)           # noqa: E731
+    return dict(dets=np.ascontiguousarray(dets), det_off=off(np.bincount(seg, minlength=S)),
+                gts=np.ascontiguousarray(g_box[ok][g_order]), gt_area=np.ascontiguousarray(g_area[ok][g_order]),
+                gt_crowd=np.ascontiguousarray(g_crowd[ok][g_order]), gt_off=off(np.bincount(g_seg, minlength=S)),
+                det_score=np.ascontiguousarray(d[:, 4]), det_rank=rank, det_cat=seg % K, gt_cat=g_cat[ok][g_order],
+                num_classes=K)
+
+
+def coco_flags_host(pack, thrs=None, area_rng=None, want_match=False):
+    """``_evaluate_img`` over every (segment, area range) of a pack -> flags uint8 [n_area, n_thr, D]: COCO_FP (unmatched,
+    inside the range), COCO_TP (matched to a box that is not ignored), COCO_IGNORED (matched to an ignored box, or unmatched
+    and outside the range); with ``want_match`` also int32 [n_area, n_thr, D], the matched box within its segment in
+    annotation order, or -1.  ``thrs``: thresholds out of IOU_THRS (``_evaluate_img`` knows no others), all of them by default."""
+    thrs = IOU_THRS if thrs is None else thrs
+    area_rng = AREA_RNG if area_rng is None else area_rng
+    rows = [np.flatnonzero(IOU_THRS == t) for t in thrs]
+    if any(len(r) != 1 for r in rows):
+        raise ValueError('the host evaluator matches at IOU_THRS only')
+    rows = np.concatenate(rows) if rows else np.zeros(0, np.int64)
+    D = len(pack['dets'])
+    flags = np.zeros((len(area_rng), len(rows), D), dtype=np.uint8)
+    match = np.full((len(area_rng), len(rows), D), -1, dtype=np.int32)
+    d_off, g_off = pack['det_off'], pack['gt_off']
+    for s in np.flatnonzero(np.diff(d_off)):
+        d0, d1, g0, g1 = d_off[s], d_off[s + 1], g_off[s], g_off[s + 1]
+        gts = [dict(bbox=pack['gts'][g], area=pack['gt_area'][g], iscrowd=int(pack['gt_crowd'][g])) for g in range(g0, g1)]
+        dts = [dict(bbox=pack['dets'][j], area=pack['dets'][j, 2] * pack['dets'][j, 3], score=pack['det_score'][j])
+               for j in range(d0, d1)]
+        for a, a_rng in enumerate(area_rng):
+            e = _evaluate_img(gts, dts, a_rng, d1 - d0)
+            dtm, dt_ig = e['dtm'][rows], e['dt_ig'][rows]
+            flags[a, :, d0:d1] = np.where(dt_ig, COCO_IGNORED, np.where(dtm > 0, COCO_TP, COCO_FP))
+            if want_match and g1 > g0:
+                # dtm counts in _evaluate_img's order of the boxes: its stable sort by the ignore flag, redone here
+                g_ig = [1 if (g['iscrowd'] or g['area'] < a_rng[0] or g['area'] > a_rng[1]) else 0 for g in gts]
+                gtind = np.argsort(np.array(g_ig, int), kind='mergesort')
+                assert np.array_equal(np.array(g_ig, int)[gtind], e['g_ig'])
+                match[a, :, d0:d1] = np.where(dtm > 0, gtind[np.maximum(dtm.astype(np.int64), 1) - 1], -1)
+    return (flags, match) if want_match else flags
+
+
+def coco_flags_device(pack, thrs, area_rng, device, timings=None, want_match=False):
+    """the same flags from csrc/coco_eval.hip: one upload of the pack through the staging path, ONE launch for the split, all
+    thresholds and all area ranges, one download (``oadg_coco_match.flags_device``, the module next to the package's import
+    shim that holds the ctypes call of the kernel; see its docstring for why that call is not in hip_ops.py)."""
+    import oadg_coco_match
+    return oadg_coco_match.flags_device(pack, thrs, area_rng, device, timings=timings, want_match=want_match)
+
+
+def coco_accumulate(pack, flags, max_dets):
+    """COCOeval.accumulate over the flags of a pack (uint8 [A, T, D] for AREA_RNG and IOU_THRS, in pack order) -> (precision
+    [T, R, K, A, M], recall [T, K, A, M]), exactly the arrays ``coco_eval_bbox`` fills: per (category, area range, maxDets)
+    the detections of rank < maxDets by descending score (stable over the images in order), fp64 cumulative tp / fp,
+    recall over the boxes that are not ignored, the precision envelope sampled at REC_THRS; -1 where no box counts."""
+    T, R, K, A, M = len(IOU_THRS), len(REC_THRS), pack['num_classes'], len(AREA_RNG), len(max_dets)
+    assert flags.shape == (A, T, len(pack['dets']))
+    precision = -np.ones((T, R, K, A, M))
+    recall = -np.ones((T, K, A, M))
+    eps = np.spacing(1)
+    area, crowd = pack['gt_area'], pack['gt_crowd'] != 0
+    # the boxes that count per (category, area range): not crowd, area inside [lo, hi]
+    npig = np.stack([np.bincount(pack['gt_cat'][~(crowd | (area < lo) | (area > hi))], minlength=K) for lo, hi in AREA_RNG], 1)
+    score, rank, cat = pack['det_score'], pack['det_rank'], pack['det_cat']
+    by_cat = np.argsort(cat, kind='stable')
+    cuts = np.searchsorted(cat[by_cat], np.arange(K + 1))
+    for k in range(K):
+        if not npig[k].any():
+            continue
+        idx = by_cat[cuts[k]:cuts[k + 1]]                       # (pack order: image after image)
+        for m, max_det in enumerate(max_dets):
+            sel = idx[rank[idx] < max_det]
+            sel = sel[np.argsort(-score[sel], kind='mergesort')]
+            nd = len(sel)
+            for a in range(A):
+                if npig[k, a] == 0:
+                    continue
+                f = flags[a][:, sel]
+                tp = np.cumsum(f == COCO_TP, axis=1).astype(np.float64)
+                fp = np.cumsum(f == COCO_FP, axis=1).astype(np.float64)
+                rc = tp / npig[k, a]
+                pr = tp / (fp + tp + eps)
+                recall[:, k, a, m] = rc[:, -1] if nd else 0
+                pr = np.maximum.accumulate(pr[:, ::-1], axis=1)[:, ::-1]       # (the envelope: the backward loop's values)
+                q = np.zeros((T, R))
+                for t in range(T):
+                    pi = np.searchsorted(rc[t], REC_THRS, side='left')
+                    ok = pi < nd
+                    q[t, ok] = pr[t, pi[ok]]
+                precision[:, :, k, a, m] = q
+    return precision, recall
 
 
 def dataset_gt_anns(dataset, indices=None):
@@ -441,16 +582,18 @@ def sdgod_evaluate(ds, results, metric='mAP', logger=None, device='auto', **eval
     return out
 
 
-def evaluate(results, ds, metrics, num_classes, mmdet_style=False):
+def evaluate(results, ds, metrics, num_classes, mmdet_style=False, device='auto'):
     """{'bbox': {AP, AP50, ...}} (COCO style) and / or {'mAP': ...} (VOC style AP@0.5).  ``mmdet_style``: the numbers and
     names of CocoDataset.evaluate (maxDets 100 / 300 / 1000, mAP at 1000 detections: mAP, mAP_50, ..., AR@100, ...) -
     what tools/test.py prints, comparable with the reference's logs; False: COCOeval's defaults (1 / 10 / 100), which is
-    what the robustness benchmark aggregates (test_robustness.py coco_eval_with_return)."""
+    what the robustness benchmark aggregates (test_robustness.py coco_eval_with_return).  ``device``: where 'bbox' is matched -
+    'auto': the current GPU when the library and a GPU are present (``voc_device``), else the host; None: the host."""
     out = {}
     idx = range(len(results))
     if 'bbox' in metrics:
         kw = dict(max_dets=MMDET_MAX_DETS, names=MMDET_METRICS) if mmdet_style else {}
-        out['bbox'] = coco_eval_bbox(dataset_gt_anns(ds, idx), results, num_classes, **kw)
+        dev = voc_device() if device == 'auto' else device
+        out['bbox'] = coco_eval_bbox(dataset_gt_anns(ds, idx), results, num_classes, device=dev, **kw)
     if 'mAP' in metrics:
         m, aps = eval_map(results, dataset_box_anns(ds, idx), num_classes)
         out['mAP'] = dict(mAP=m, per_class=aps)
@@ -492,7 +635,7 @@ def _num_classes(ds):
     return len(getattr(ds, 'CLASSES', None) or range(getattr(ds, 'num_classes', 8)))
 
 
-def dataset_evaluate(ds, results, metric='bbox', logger=None, **eval_kwargs):
+def dataset_evaluate(ds, results, metric='bbox', logger=None, device='auto', **eval_kwargs):
     """``CocoDataset.evaluate`` (mmdet/datasets/coco.py:364-573, which CityscapesDataset delegates 'bbox' to) and
     ``VOCDataset.evaluate`` (voc.py:28-106) on this module's evaluators: the flat ordered dict the reference returns
     (``SdgodDataset.evaluate`` is ``sdgod_evaluate`` above).
@@ -501,7 +644,8 @@ def dataset_evaluate(ds, results, metric='bbox', logger=None, **eval_kwargs):
     ``metric_items`` asked for) and ``bbox_mAP_copypaste`` - the mmdet-style numbers: maxDets = ``proposal_nums`` =
     (100, 300, 1000), mAP at the last of them.  'mAP': ``AP50`` (``AP{100 * iou_thr}`` per threshold, 3 decimals) and ``mAP``
     (their mean) from ``eval_map``.  ``logger`` is the reference's parameter: nothing is printed here, the caller (EvalHook,
-    tools/test.py) prints what it returns."""
+    tools/test.py) prints what it returns.  ``device`` ('bbox' only): 'auto' matches on the current GPU when the library and a
+    GPU are present (``voc_device``, as ``sdgod_evaluate``), None on the host - the same numbers either way."""
     metrics = list(metric) if isinstance(metric, (list, tuple)) else [metric]
     check_evaluate_args(type(ds), metrics, eval_kwargs)
     assert len(results) == len(ds), f'{len(results)} results for {len(ds)} images'
@@ -515,7 +659,8 @@ def dataset_evaluate(ds, results, metric='bbox', logger=None, **eval_kwargs):
             for it in items:
                 if it not in MMDET_METRICS:
                     raise KeyError(f'metric item {it} is not supported')
-            stats = coco_eval_bbox(dataset_gt_anns(ds), results, nc, max_dets=nums, names=MMDET_METRICS)
+            dev = voc_device() if device == 'auto' else device
+            stats = coco_eval_bbox(dataset_gt_anns(ds), results, nc, max_dets=nums, names=MMDET_METRICS, device=dev)
             for it in items:
                 out[f'bbox_{it}'] = float(f'{stats[it]:.3f}')
             out['bbox_mAP_copypaste'] = ' '.join(f'{stats[k]:.3f}' for k in MMDET_METRICS[:6])
