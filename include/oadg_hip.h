@@ -403,6 +403,35 @@ int oadg_coco_match(const double* dets, const int32_t* det_off, const double* gt
                     int32_t* match, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Confusion counts of a test split (csrc/confusion.hip)
+ *   replaces tools/analysis_tools/confusion_matrix.py:95-142 analyze_per_img_dets + bbox_overlaps.py, one Python triple
+ *   loop (classes x detections x boxes) per image
+ * A segment is one IMAGE, n_seg of them.  dets: fp32 [n_det][4] = x1, y1, x2, y2, 16-byte aligned, concatenated in segment
+ * order - the detections that passed the score threshold, all classes of an image together; det_cls: int32 [n_det], the class
+ * of each; det_off: int32 [n_seg + 1]; gts: fp32 [n_gt][4], 16-byte aligned; gt_lab: int32 [n_gt]; gt_off: int32 [n_seg + 1].
+ * Offsets are clamped to the arrays' extents before use; a class or label outside [0, num_classes) takes no part.
+ * counts: int64 [num_classes + 1][num_classes + 1], row = label of the box, column = class of the detection, the last row
+ * and column the background.  The call zeroes it, then per image: a detection of class c adds 1 to counts[gt_lab[j]][c] for
+ * EVERY box j of the image whose fp32 IoU (modern extents, the operation order of bbox_overlaps.py without contraction,
+ * correctly rounded) is >= tp_iou_thr, or 1 to counts[C][c] when there is none; a box that no detection of its OWN label
+ * matched adds 1 to counts[gt_lab[j]][C].  Nothing is claimed: several detections may match one box, one detection several
+ * boxes, and all are counted.  Integers only: the same numbers from run to run, whatever the order of the atomic adds.
+ * Boxes pass through LDS OADG_CONFUSION_CHUNK at a time; the counts of an image are kept in LDS while (num_classes + 1)^2 <=
+ * OADG_CONFUSION_LDS_CELLS (beyond: global atomic adds), the "found" words of its boxes while it has at most
+ * OADG_CONFUSION_LDS_BOXES (beyond: the workspace).  1 <= num_classes <= OADG_CONFUSION_MAX_CLASSES.
+ * The workspace (4-byte aligned) must hold oadg_confusion_workspace_bytes(...) bytes (0: arguments the call refuses);
+ * OADG_ESIZE when it is smaller, OADG_EARG for any other bad argument - neither writes or launches anything.  One launch for
+ * the split.  Called from oadg_confusion.py only (the device half of evaluation.calculate_confusion_matrix(device=...)). */
+#define OADG_CONFUSION_CHUNK 128
+#define OADG_CONFUSION_LDS_BOXES 512
+#define OADG_CONFUSION_LDS_CELLS 8192
+#define OADG_CONFUSION_MAX_CLASSES 4096
+size_t oadg_confusion_workspace_bytes(int n_seg, int n_det, int n_gt, int num_classes);
+int oadg_confusion_count(const float* dets, const int32_t* det_cls, const int32_t* det_off, const float* gts,
+                         const int32_t* gt_lab, const int32_t* gt_off, int n_seg, int n_det, int n_gt, int num_classes,
+                         float tp_iou_thr, int64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * PNG output: a resident batch -> the zlib stream of every image, and the stream -> a file (csrc/png_encode.hip)
  *   replaces save_data  tools/analysis_tools/get_corrupted_dataset.py:83-113 (PIL.Image.fromarray(img).save(path): PNG row
  *            filtering and zlib deflate of every corrupted image on one host core)

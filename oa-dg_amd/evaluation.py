@@ -600,6 +600,270 @@ def evaluate(results, ds, metrics, num_classes, mmdet_style=False, device='auto'
     return out
 
 
+# ------------------------------------------------------------------------------------------ per-image mAP
+# tools/analysis_tools/analyze_results.py:14-46 ``bbox_map_eval``: the mean over ten thresholds of ``eval_map`` on ONE image
+# (modern coordinates, area-mode AP, ignored boxes honoured), once per image of the split.  Here the whole split is packed once
+# (pack_voc_segments), matched by the flags functions above - one launch per VOC_MAX_THRS thresholds on the device - and only
+# the accumulation runs per image.
+def voc_accumulate_per_image(pack, flags, dataset=None):
+    """``voc_accumulate`` image by image: ``flags`` uint8 [D] (one threshold, pack order) -> float64 [n_images], or [T, D] ->
+    [T, n_images]; for every image i exactly ``eval_map_voc([results[i]], [annotations[i]], ...)[0]``: per class of the image
+    that has a regular box the AP of its own detections (stable descending score, fp32 cumulative tp / fp, recall over the
+    regular boxes), their fp32 mean; 0.0 for an image without a regular box.  Classes without a regular box are skipped, as
+    there.  A segment is sorted once for all thresholds, and the area under the envelope is ``average_precision``'s own
+    arithmetic with the envelope taken by a running maximum instead of its loop (the same values: a maximum selects)."""
+    C, dets, d_off, g_reg = pack['num_classes'], pack['dets'], pack['det_off'], pack['gt_reg']
+    n = len(g_reg) // C
+    flags = np.asarray(flags)
+    many = flags.ndim == 2
+    flags = flags if many else flags[None]
+    T = len(flags)
+    eps = np.finfo(np.float32).eps
+    out = np.zeros((T, n), dtype=np.float64)
+    aps = [[] for _ in range(n)]                                      # per image: a row [T] of fp32 APs per class with a box
+    for s in np.flatnonzero(g_reg > 0):
+        d0, d1 = d_off[s], d_off[s + 1]
+        num_gts = np.zeros(1, dtype=int)
+        num_gts[0] = g_reg[s]
+        sort_inds = np.argsort(-dets[d0:d1, 4], kind='stable')
+        f = flags[:, d0:d1][:, sort_inds]
+        tp = np.cumsum((f == FLAG_TP).astype(np.float32), axis=1)
+        fp = np.cumsum((f == FLAG_FP).astype(np.float32), axis=1)
+        recalls = tp / np.maximum(num_gts[:, np.newaxis], eps)            # [T, m] float64, as voc_accumulate's
+        precisions = tp / np.maximum((tp + fp), eps)                      # [T, m] float32
+        if dataset == 'voc07':
+            ap = [np.float32(average_precision(recalls[t], precisions[t], '11points')) for t in range(T)]
+        else:
+            zeros, ones = np.zeros((T, 1)), np.ones((T, 1))
+            mrec = np.concatenate([zeros, recalls, ones], axis=1)
+            mpre = np.concatenate([zeros, precisions, zeros], axis=1)
+            mpre = np.maximum.accumulate(mpre[:, ::-1], axis=1)[:, ::-1]
+            ap = []
+            for t in range(T):
+                ind = np.where(mrec[t, 1:] != mrec[t, :-1])[0]
+                ap.append(np.float32(float(np.sum((mrec[t, ind + 1] - mrec[t, ind]) * mpre[t, ind + 1]))))
+        aps[s // C].append(ap)
+    for i, a in enumerate(aps):
+        if a:
+            out[:, i] = [np.array(col).mean().item() for col in zip(*a)]
+    return out if many else out[0]
+
+
+def per_image_map(results, annotations, num_classes, device=None):
+    """``bbox_map_eval`` for every image of a split -> float64 [n_images]: the mean over np.linspace(.5, .95, 10) of the
+    one-image ``eval_map`` (dataset=None, modern coordinates).  results: per image the per-class list (or the (bbox, segm)
+    tuple: its bbox part); annotations: per image the ``get_ann_info`` dict.  ONE pack for the split and all thresholds;
+    ``device=None``: ``voc_flags_host``; a torch device: csrc/voc_eval.hip - the same flags, so the same numbers."""
+    results = [r[0] if isinstance(r, tuple) else r for r in results]
+    thrs = [_f32_at_least(t) for t in IOU_THRS]
+    pack = pack_voc_segments(results, annotations, num_classes)
+    total = np.zeros(len(results), dtype=np.float64)
+    for k in range(0, len(thrs), VOC_MAX_THRS):
+        part = thrs[k:k + VOC_MAX_THRS]
+        flags = voc_flags_host(pack, part, False) if device is None else voc_flags_device(pack, part, False, device)
+        for per_thr in voc_accumulate_per_image(pack, flags):
+            total = total + per_thr                                        # (sum(mean_aps): left to right, from 0)
+    return total / len(thrs)
+
+
+def _f32_at_least(t):
+    """the smallest fp32 value >= ``t``.  ``bbox_map_eval`` hands eval_map np.float64 thresholds (np.linspace), so the
+    reference compares its fp32 IoUs with them in float64 - under every numpy; for fp32 IoUs that is exactly the fp32
+    comparison with this value, which the flags functions (and the kernel) take as it is: np.float32 of it changes nothing.
+    (0.7 -> the fp32 above fp32(0.7): an IoU of exactly fp32(0.7) = 0.699999988 is below the float64 0.7.)"""
+    f = np.float32(t)
+    if float(f) < float(t):
+        f = np.nextafter(f, np.float32(np.inf))
+    return float(f)
+
+
+def rank_images(maps, topk=20):
+    """analyze_results.py:108-130: (good, bad) lists of (index, mAP) - a STABLE ascending sort (equal mAPs keep the order of
+    the images), ``bad`` its first ``topk`` and ``good`` its last ``topk``; ``topk`` becomes len // 2 when 2 * topk > len"""
+    assert topk > 0
+    if topk * 2 > len(maps):
+        topk = len(maps) // 2
+    ranked = sorted(((i, float(m)) for i, m in enumerate(maps)), key=lambda kv: kv[1])
+    return ranked[-topk:], ranked[:topk]       # (a split of one image: topk 0, and [-0:] is that image - as the reference)
+
+
+# ------------------------------------------------------------------------------------------ confusion matrix
+# tools/analysis_tools/confusion_matrix.py:59-142.  ``confusion_per_image`` is the reference's loop (the yardstick, pinned to
+# the reference's own output by tests/golden/result_analysis_reference.npz); the product path packs the split once - one
+# segment per IMAGE - and counts it on the host (vectorised per image) or in one launch of csrc/confusion.hip.  The same two
+# rules are FIXED as in the VOC protocol: the thresholds are rounded to fp32 and compared in fp32.
+def confusion_per_image(cm, gt_bboxes, gt_labels, result, score_thr=0, tp_iou_thr=0.5, nms_iou_thr=None):
+    """confusion_matrix.py:95-142 ``analyze_per_img_dets``: adds one image to ``cm`` [(C + 1), (C + 1)] (row: label of the
+    box, column: class of the detection, the last of each: background).  A detection of class c with score >= score_thr
+    adds 1 to cm[gt_label[j], c] for EVERY box j with iou >= tp_iou_thr, whatever its label, or 1 to cm[C, c] without one; a
+    box that no detection of its own label matched adds 1 to cm[gt_label, C].  Nothing is claimed, ``bboxes_ignore`` takes no
+    part.  ``nms_iou_thr`` (truthy): mmcv's nms(..., score_threshold=score_thr) per class first."""
+    C = cm.shape[0] - 1
+    gt_bboxes = np.asarray(gt_bboxes, dtype=np.float32).reshape(-1, 4)
+    gt_labels = _checked_labels(gt_labels, C)
+    if len(result) != C or len(gt_labels) != len(gt_bboxes):
+        raise ValueError(f'{len(result)} classes of detections for a {C}-class matrix, or labels that do not match the boxes')
+    thr, s_thr = np.float32(tp_iou_thr), np.float32(score_thr)
+    true_positives = np.zeros(len(gt_labels), dtype=np.int64)
+    for det_label, det_bboxes in enumerate(result):
+        det_bboxes = np.asarray(det_bboxes, dtype=np.float32).reshape(-1, 5)
+        if nms_iou_thr:
+            det_bboxes = nms_host(det_bboxes, nms_iou_thr, score_thr)
+        ious = bbox_overlaps_voc(det_bboxes[:, :4], gt_bboxes)
+        for i, det_bbox in enumerate(det_bboxes):
+            det_match = 0
+            if det_bbox[4] >= s_thr:
+                for j, gt_label in enumerate(gt_labels):
+                    if ious[i, j] >= thr:
+                        det_match += 1
+                        if gt_label == det_label:
+                            true_positives[j] += 1
+                        cm[gt_label, det_label] += 1
+                if det_match == 0:
+                    cm[C, det_label] += 1
+    for num_tp, gt_label in zip(true_positives, gt_labels):
+        if num_tp == 0:
+            cm[gt_label, C] += 1
+
+
+def _checked_labels(labels, num_classes):
+    labels = np.asarray(labels).reshape(-1).astype(np.int64)
+    if len(labels) and (labels.min() < 0 or labels.max() >= num_classes):
+        raise ValueError(f'box label outside [0, {num_classes}): {labels[(labels < 0) | (labels >= num_classes)][:4].tolist()} '
+                         f'(the reference would wrap a negative index silently)')
+    return labels
+
+
+def nms_host(dets, iou_thr, score_thr=0):
+    """mmcv.ops.nms(boxes, scores, iou_thr, score_threshold=score_thr) of one class: the rows [k, 5] with score > score_thr
+    (strictly), by descending score (stable), greedily suppressed where the fp32 IoU = inter / (area_i + area_j - inter)
+    (offset 0) is > iou_thr -> the kept rows, in that order"""
+    d = np.asarray(dets, dtype=np.float32).reshape(-1, 5)
+    d = d[d[:, 4] > np.float32(score_thr)]
+    d = d[np.argsort(-d[:, 4], kind='stable')]
+    x1, y1, x2, y2 = d[:, 0], d[:, 1], d[:, 2], d[:, 3]
+    area = (x2 - x1) * (y2 - y1)
+    thr = np.float32(iou_thr)
+    removed = np.zeros(len(d), dtype=bool)
+    keep = []
+    for i in range(len(d)):
+        if removed[i]:
+            continue
+        keep.append(i)
+        w = np.maximum(np.minimum(x2[i], x2[i + 1:]) - np.maximum(x1[i], x1[i + 1:]), np.float32(0))
+        h = np.maximum(np.minimum(y2[i], y2[i + 1:]) - np.maximum(y1[i], y1[i + 1:]), np.float32(0))
+        inter = w * h
+        with np.errstate(divide='ignore', invalid='ignore'):
+            removed[i + 1:] |= inter / ((area[i] + area[i + 1:]) - inter) > thr
+    return d[keep]
+
+
+def _aligned16(a):
+    """``a`` contiguous at an address that is a multiple of 16 (the kernels read boxes 16 bytes at a time)"""
+    a = np.ascontiguousarray(a)
+    if a.ctypes.data % 16 == 0:
+        return a
+    buf = np.empty(a.nbytes + 16, dtype=np.uint8)
+    off = -buf.ctypes.data % 16
+    out = buf[off:off + a.nbytes].view(a.dtype).reshape(a.shape)
+    out[...] = a
+    return out
+
+
+def pack_confusion_segments(results, annotations, num_classes, score_thr=0):
+    """a split as the arrays of oadg_confusion_count: one segment per IMAGE.  dict(dets fp32 [D, 4] - per image class after
+    class, within a class in the result's order, only the rows with score >= score_thr (fp32) -, det_cls int32 [D], det_off
+    int32 [n + 1], gts fp32 [G, 4] in annotation order, gt_lab int32 [G], gt_off int32 [n + 1], num_classes); the box arrays
+    start at multiples of 16 bytes.  annotations: per image the ``get_ann_info`` dict (bboxes, labels; the ignored boxes take
+    no part).  ValueError: a label outside [0, num_classes), a result that has not num_classes arrays, lengths that differ."""
+    n, C = len(results), int(num_classes)
+    if len(annotations) != n:
+        raise ValueError(f'{n} results for {len(annotations)} annotations')
+    s_thr = np.float32(score_thr)
+    dets, cls, d_cnt, boxes, labels, g_cnt = [], [], np.zeros(n, np.int64), [], [], np.zeros(n, np.int64)
+    for i, (res, ann) in enumerate(zip(results, annotations)):
+        if isinstance(res, tuple):
+            res = res[0]
+        if len(res) != C:
+            raise ValueError(f'image {i}: {len(res)} classes of detections, num_classes is {C}')
+        for c, d in enumerate(res):
+            d = np.asarray(d, dtype=np.float32).reshape(-1, 5)
+            d = d[d[:, 4] >= s_thr]
+            dets.append(d[:, :4])
+            cls.append(np.full(len(d), c, dtype=np.int32))
+            d_cnt[i] += len(d)
+        b = np.asarray(ann['bboxes'], dtype=np.float32).reshape(-1, 4)
+        l = _checked_labels(ann['labels'], C)
+        if len(b) != len(l):
+            raise ValueError(f'image {i}: {len(b)} boxes with {len(l)} labels')
+        boxes.append(b)
+        labels.append(l.astype(np.int32))
+        g_cnt[i] = len(b)
+    cat = lambda xs, shape, dt: np.concatenate(xs + [np.zeros(shape, dt)])          # noqa: E731
+    off = lambda c: np.concatenate([[0], np.cumsum(c)]).astype(np.int32)           # noqa: E731
+    assert d_cnt.sum() < 2 ** 31 and g_cnt.sum() < 2 ** 31
+    return dict(dets=_aligned16(cat(dets, (0, 4), np.float32)), det_cls=np.ascontiguousarray(cat(cls, (0,), np.int32)),
+                det_off=off(d_cnt), gts=_aligned16(cat(boxes, (0, 4), np.float32)),
+                gt_lab=np.ascontiguousarray(cat(labels, (0,), np.int32)), gt_off=off(g_cnt), num_classes=C)
+
+
+def confusion_counts_host(pack, tp_iou_thr=0.5):
+    """the counts of a pack on the host -> int64 [(C + 1), (C + 1)]: ``confusion_per_image``'s rules, one IoU matrix per
+    image (all classes of its detections together)"""
+    C = pack['num_classes']
+    cm = np.zeros((C + 1, C + 1), dtype=np.int64)
+    thr = np.float32(tp_iou_thr)
+    d_off, g_off = pack['det_off'], pack['gt_off']
+    for i in range(len(d_off) - 1):
+        d, c = pack['dets'][d_off[i]:d_off[i + 1]], pack['det_cls'][d_off[i]:d_off[i + 1]].astype(np.int64)
+        g, l = pack['gts'][g_off[i]:g_off[i + 1]], pack['gt_lab'][g_off[i]:g_off[i + 1]].astype(np.int64)
+        hit = bbox_overlaps_voc(d, g) >= thr                                       # [m, k]
+        di, gj = np.nonzero(hit)
+        np.add.at(cm, (l[gj], c[di]), 1)
+        np.add.at(cm, (np.full(int((~hit.any(axis=1)).sum()), C), c[~hit.any(axis=1)]), 1)
+        found = (hit & (c[:, None] == l[None, :])).any(axis=0)
+        np.add.at(cm, (l[~found], np.full(int((~found).sum()), C)), 1)
+    return cm
+
+
+def confusion_counts_device(pack, tp_iou_thr, device):
+    """the same counts from csrc/confusion.hip: one upload of the pack through the staging path, ONE launch for the split, one
+    download (``oadg_confusion.counts_device``, the module next to the package's import shim that holds the ctypes call of
+    the kernel; see its docstring for why that call is not in hip_ops.py)."""
+    import oadg_confusion
+    return oadg_confusion.counts_device(pack, tp_iou_thr, device)
+
+
+def dataset_ann_infos(dataset, indices=None):
+    """per image the ``get_ann_info`` dict of a file dataset; ``boxes`` of the synthetic one in that form"""
+    idx = range(len(dataset)) if indices is None else indices
+    if hasattr(dataset, 'get_ann_info'):
+        return [dataset.get_ann_info(i) for i in idx]
+    return [dict(zip(('bboxes', 'labels'), dataset.boxes(i))) for i in idx]
+
+
+def calculate_confusion_matrix(dataset, results, score_thr=0, nms_iou_thr=None, tp_iou_thr=0.5, device='auto'):
+    """confusion_matrix.py:59-92: the float64 [(C + 1), (C + 1)] matrix of a split (C = len(dataset.CLASSES)).  Results
+    given as (bbox, segm) tuples use the bbox part.  A truthy ``nms_iou_thr`` reruns NMS per (image, class) first, with
+    mmcv's nms(..., score_threshold=score_thr) semantics - on the batched NMS kernel when matching on a device.  ``device``:
+    'auto' counts on the current GPU when the library and a GPU are present (``voc_device``), None on the host - the same
+    numbers either way."""
+    C = _num_classes(dataset)
+    if len(dataset) != len(results):
+        raise ValueError(f'{len(results)} results for {len(dataset)} images')
+    results = [r[0] if isinstance(r, tuple) else r for r in results]
+    dev = voc_device() if device == 'auto' else device
+    if nms_iou_thr:
+        if dev is None:
+            results = [[nms_host(d, nms_iou_thr, score_thr) for d in res] for res in results]
+        else:
+            import oadg_confusion
+            results = oadg_confusion.nms_results_device(results, nms_iou_thr, score_thr, dev)
+    pack = pack_confusion_segments(results, dataset_ann_infos(dataset), C, score_thr)
+    counts = confusion_counts_host(pack, tp_iou_thr) if dev is None else confusion_counts_device(pack, tp_iou_thr, dev)
+    return counts.astype(np.float64)
+
+
 # ------------------------------------------------------------------------------------------ dataset.evaluate
 # What ``dataset.evaluate(results, metric=..., **eval_kwargs)`` of the reference takes per protocol, and what of it this
 # build computes.  A metric or keyword of the reference that is not built is rejected BY NAME (NotImplementedError), one the
