@@ -432,6 +432,34 @@ int oadg_confusion_count(const float* dets, const int32_t* det_cls, const int32_
                          float tp_iou_thr, int64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Proposal recall: the greedy bipartite matching of a whole test split, every proposal budget at once (csrc/recall.hip)
+ *   replaces _recalls  mmdet/core/evaluation/recall.py:11-41 (per image and budget G rounds, each an argmax over a G x P
+ *            matrix and the rewrite of a row and a column) and bbox_overlaps  mmdet/core/evaluation/bbox_overlaps.py:5-65
+ * n_img images.  props: fp32 [n_prop][4] = x1, y1, x2, y2, 16-byte aligned, per image in evaluation order (descending score)
+ * and already cut to the largest budget; prop_off: int32 [n_img + 1]; gts: fp32 [n_gt][4], 16-byte aligned; gt_off: int32
+ * [n_img + 1].  Offsets are clamped to the arrays' extents before use.  nums_host: n_nums <= OADG_RECALL_MAX_NUMS budgets in
+ * HOST memory (read during the call); legacy != 0: widths and heights are x2 - x1 + 1, in the IoU too.
+ *   out: fp32 [n_nums][n_gt].  Row k, slice gt_off[i] .. gt_off[i+1], holds for image i and its first n = min(nums[k], P_i)
+ *     proposals the values gt_ious[j] of _recalls IN ROUND ORDER j = 0, 1, ... (not by box): round j takes, over the boxes and
+ *     proposals still live, the largest fp32 IoU (operation order of bbox_overlaps.py without contraction, correctly rounded) -
+ *     per box the lowest proposal that attains its maximum, among the boxes the lowest that attains the largest maximum -,
+ *     records it and retires that box and that proposal (a box whose best IoU is 0 retires the lowest live proposal).  Once
+ *     no proposal is live every remaining round records -1; n == 0 records 0 for every box.  Every element that belongs to a
+ *     box of an image is written; the same bytes from run to run.  Inputs are finite (nothing is promised for a NaN).
+ * No G x P matrix is stored: proposals are staged in LDS while n <= OADG_RECALL_LDS_PROPS and the per-box state while the
+ * image has at most OADG_RECALL_LDS_GTS boxes; beyond, that state lives in the workspace (8-byte aligned), which must hold
+ * oadg_recall_match_workspace_bytes(...) = n_nums * (8 * n_gt + n_prop) bytes (0: arguments the call refuses); OADG_ESIZE
+ * when it is smaller.  One launch for the split and all budgets.  Called from oadg_recall.py only (the device half of
+ * evaluation.eval_recalls(device=...)). */
+#define OADG_RECALL_LDS_PROPS 1024
+#define OADG_RECALL_LDS_GTS 256
+#define OADG_RECALL_MAX_NUMS 16
+size_t oadg_recall_match_workspace_bytes(int n_img, int n_prop, int n_gt, int n_nums);
+int oadg_recall_match(const float* props, const int32_t* prop_off, const float* gts, const int32_t* gt_off, int n_img,
+                      int n_prop, int n_gt, const int32_t* nums_host, int n_nums, int legacy, float* out, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * PNG output: a resident batch -> the zlib stream of every image, and the stream -> a file (csrc/png_encode.hip)
  *   replaces save_data  tools/analysis_tools/get_corrupted_dataset.py:83-113 (PIL.Image.fromarray(img).save(path): PNG row
  *            filtering and zlib deflate of every corrupted image on one host core)

@@ -67,6 +67,8 @@ VOC_MAX_THRS = 8
 COCO_MAX_LANES, COCO_LDS_GTS, COCO_LDS_DETS = 64, 128, 64   # csrc/coco_eval.hip: matchings of one call, staging capacities
 # csrc/confusion.hip: boxes staged per pass, boxes whose "found" words fit in LDS, (C + 1)^2 cells counted in LDS, largest C
 CONFUSION_CHUNK, CONFUSION_LDS_BOXES, CONFUSION_LDS_CELLS, CONFUSION_MAX_CLASSES = 128, 512, 8192, 4096
+# csrc/recall.hip: proposals of an (image, budget) staged in LDS, boxes whose matching state fits in LDS, budgets of one call
+RECALL_LDS_PROPS, RECALL_LDS_GTS, RECALL_MAX_NUMS = 1024, 256, 16
 
 
 class RegionOp(Structure):
@@ -257,6 +259,8 @@ SIGNATURES = {
     'oadg_coco_match': (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, POINTER(cd), ci, POINTER(cd), ci, vp, vp, vp, cs, vp]),
     'oadg_confusion_workspace_bytes': (cs, [ci, ci, ci, ci]),
     'oadg_confusion_count': (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, vp, vp, cs, vp]),
+    'oadg_recall_match_workspace_bytes': (cs, [ci, ci, ci, ci]),
+    'oadg_recall_match': (ci, [vp, vp, vp, vp, ci, ci, ci, POINTER(c_int32), ci, ci, vp, vp, cs, vp]),
     'oadg_png_encode_stream_capacity': (cs, [ci, ci]),
     'oadg_png_encode_segments': (ci, [ci, ci]),
     'oadg_png_encode_workspace_bytes': (cs, [ci, ci, ci]),

@@ -148,6 +148,11 @@ class CocoDataset:
         """coco.py:364-573 for 'bbox' (XMLDataset: voc.py:28-106 for 'mAP'): evaluation.dataset_evaluate"""
         return evaluation.dataset_evaluate(self, results, metric=metric, logger=logger, **eval_kwargs)
 
+    def fast_eval_recall(self, results, proposal_nums, iou_thrs, logger=None, device='auto'):
+        """coco.py:312-334: per budget the recall of one [n, 5] array of proposals per image, averaged over ``iou_thrs``
+        (evaluation.fast_eval_recall; matched on the GPU when there is one)"""
+        return evaluation.fast_eval_recall(self, results, proposal_nums, iou_thrs, logger=logger, device=device)
+
     def get_ann_info(self, idx):
         img_id = self.data_infos[idx]['id']
         return self._parse_ann_info(self.data_infos[idx], self.coco.load_anns(self.coco.get_ann_ids(img_ids=[img_id])))
@@ -415,6 +420,7 @@ class SdgodDataset(XMLDataset):
     reference's VOC protocol (evaluation.sdgod_evaluate): legacy "+ 1" coordinates, ``difficult`` objects as ignore regions
     and, for a VOC2007 prefix, the 11-point AP - matched on the GPU (csrc/voc_eval.hip) when there is one."""
     CLASSES = ('bus', 'bike', 'car', 'motor', 'person', 'rider', 'truck')
+    RECALL_LEGACY_COORDINATE = True      # sdgod.py:92-98: 'recall' with the VOC devkit's "+ 1" extents (evaluation.proposal_evaluate)
 
     def __init__(self, **kwargs):
         super().__init__(**kwargs)

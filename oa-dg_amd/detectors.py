@@ -408,3 +408,81 @@ class TwoStageDetector(BaseDetector):
 @DETECTORS.register_module()
 class FasterRCNN(TwoStageDetector):
     pass
+
+
+@DETECTORS.register_module()
+class RPN(BaseDetector):
+    """mmdet/models/detectors/rpn.py: backbone, neck and RPN head alone; a test returns the PROPOSALS of every image as one
+    numpy [n, 5] array (x1, y1, x2, y2, score; best first).  Its use here is scoring the first stage of a trained
+    Faster R-CNN (evaluation.proposal_evaluate, tools/test.py --eval proposal_fast): such a checkpoint loads into it, its
+    ``roi_head.*`` tensors are merely unexpected.  Training an RPN on its own is not built."""
+
+    def __init__(self, backbone, neck, rpn_head, train_cfg, test_cfg, pretrained=None, init_cfg=None, roi_head=None):
+        super().__init__(init_cfg)
+        # (``roi_head``: not the reference's; a config that inherits a Faster R-CNN's model cannot remove the key and sets None)
+        if roi_head is not None:
+            raise TypeError('an RPN detector has no roi_head (set roi_head=None in a config that inherits one)')
+        if pretrained:
+            backbone = dict(backbone, pretrained=pretrained)
+        self.backbone = build_backbone(backbone)
+        self.neck = build_neck(neck) if neck is not None else None
+        rpn_head_ = dict(rpn_head)
+        rpn_head_.update(train_cfg=train_cfg.rpn if train_cfg is not None else None, test_cfg=test_cfg.rpn)
+        self.rpn_head = build_head(rpn_head_)
+        self.train_cfg, self.test_cfg = train_cfg, test_cfg
+
+    with_neck = property(lambda self: self.neck is not None)
+
+    def init_weights(self, allow_missing_pretrained=None):
+        self.backbone.init_weights(allow_missing_pretrained)
+
+    def extract_feat(self, img):
+        x = self.backbone(img)
+        if self.with_neck:
+            x = self.neck(x)
+        return x
+
+    def forward_dummy(self, img):
+        return self.rpn_head(self.extract_feat(img))
+
+    def forward_train(self, img, img_metas, gt_bboxes=None, gt_bboxes_ignore=None, **kwargs):
+        raise NotImplementedError('RPN.forward_train is not built: the RPN detector scores the first stage of a trained '
+                                  'Faster R-CNN (load its checkpoint); train the FasterRCNN config instead')
+
+    @torch.no_grad()
+    def simple_test(self, img, img_metas, rescale=False):
+        """rpn.py:91-115: with ``rescale`` the boxes are divided by the image's ``scale_factor``"""
+        proposal_list = self.rpn_head.simple_test_rpn(self.extract_feat(img), img_metas)
+        if rescale:
+            for proposals, meta in zip(proposal_list, img_metas):
+                proposals[:, :4] /= proposals.new_tensor(meta['scale_factor'])
+        return [proposal.cpu().numpy() for proposal in proposal_list]
+
+    @torch.no_grad()
+    def aug_test(self, imgs, img_metas, rescale=False):
+        """rpn.py:117-140: the merged proposals live in the original image's frame; without ``rescale`` they are mapped
+        into the frame of imgs[0]"""
+        from .core.post_processing import bbox_mapping
+        proposal_list = self.rpn_head.aug_test_rpn([self.extract_feat(img) for img in imgs], img_metas)
+        if not rescale:
+            for proposals, meta in zip(proposal_list, img_metas[0]):
+                proposals[:, :4] = bbox_mapping(proposals[:, :4], meta['img_shape'], meta['scale_factor'], meta['flip'],
+                                                meta.get('flip_direction') or 'horizontal')
+        return [proposal.cpu().numpy() for proposal in proposal_list]
+
+    def show_result(self, data, result, top_k=20, **kwargs):
+        """rpn.py:142-159: the first ``top_k`` proposals (all when top_k <= 0) drawn over a copy of ``data`` on the device, as
+        one class named 'proposal' with no score threshold (``score_thr`` is dropped, as there; ``bbox_color`` defaults to
+        green).  Writes a PNG when ``out_file`` is given, returns the drawn BGR numpy image when it is not."""
+        kwargs.pop('score_thr', None)
+        color = kwargs.pop('bbox_color', 'green')
+        kwargs.pop('text_color', None)
+        if kwargs.pop('show', False):
+            raise NotImplementedError("show_result(show=True) is not built: there is no window here; pass out_file=... or "
+                                      "take the returned image")
+        from . import visualization
+        param = next(self.parameters(), None)
+        device = param.device if param is not None and param.is_cuda else torch.device('cuda', torch.cuda.current_device())
+        result = np.asarray(result, dtype=np.float32).reshape(-1, 5)
+        return visualization.show_result(data, [result[:top_k] if top_k > 0 else result], ('proposal',), device, score_thr=0,
+                                         bbox_color=color, text_color=color, **kwargs)

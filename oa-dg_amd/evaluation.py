@@ -11,6 +11,11 @@ the twelve summary numbers.  It is pinned by hand-computed cases (tests/test_eva
 The VOC protocol of the Diverse-Weather benchmark (``SdgodDataset.evaluate`` -> mmdet/core/evaluation/mean_ap.py ``eval_map``
 with 'voc07' and the legacy coordinates) is ``eval_map_voc`` below: host functions pinned to the reference's own output
 (tests/golden/voc_eval_reference.npz) and the same matching on the GPU (csrc/voc_eval.hip).
+
+The recall of PROPOSALS (mmdet/core/evaluation/recall.py ``eval_recalls``; the 'proposal', 'proposal_fast' and 'recall' metrics
+of the reference's datasets, for the results of an 'RPN' detector) is ``eval_recalls`` / ``proposal_evaluate`` below: host
+functions pinned to the reference's own output (tests/golden/recall_reference.npz) and the same matching on the GPU
+(csrc/recall.hip).
 """
 import os
 
@@ -864,6 +869,258 @@ def calculate_confusion_matrix(dataset, results, score_thr=0, nms_iou_thr=None, 
     return counts.astype(np.float64)
 
 
+# ------------------------------------------------------------------------------------------ proposal recall
+# mmdet/core/evaluation/recall.py as CocoDataset.evaluate 'proposal_fast' (coco.py:312-334, 426-435) and the VOC-style
+# datasets' 'recall' (sdgod.py:90-105, custom.py:359-369) drive it: per image and per proposal budget Hosang's greedy
+# bipartite matching of boxes to proposals, then the fraction of boxes matched at each IoU threshold.  The host functions
+# below are the yardstick (pinned to the reference's own output by tests/golden/recall_reference.npz) and the path without a
+# GPU; csrc/recall.hip computes the same matched IoUs for a whole split and all budgets in one launch.  Two rules are FIXED
+# here where the reference leaves them to numpy: equal scores are ordered lowest index first (a stable
+# sort; the reference's ``argsort()[::-1]`` is whatever numpy's quicksort leaves), and an fp32 IoU is promoted to fp64 before
+# it is compared with the fp64 threshold (numpy 2's rule; numpy 1 compared in fp32).
+def pack_recall(gts, proposals, proposal_nums):
+    """a split as the arrays of oadg_recall_match.  gts: per image [g, 4] boxes or None; proposals: per image [n, 5] (sorted
+    here by descending score, equal scores lowest index first) or [n, 4] (kept in their order), cut to ``proposal_nums[-1]``
+    (recall.py:94-109).  dict(props fp32 [P, 4], prop_off int32 [N + 1], gts fp32 [G, 4], gt_off int32 [N + 1], nums int32
+    [K] = min(num, proposal_nums[-1]), the budget that ``ious[:, :num]`` really leaves); the box arrays start at multiples of
+    16 bytes.  ValueError: a coordinate that is not finite in fp32, or a NaN score."""
+    nums = [int(v) for v in np.asarray(proposal_nums).reshape(-1)]
+    if not nums or min(nums) < 0:
+        raise ValueError(f'proposal_nums must hold at least one budget, none negative (got {nums})')
+    if len(gts) != len(proposals):
+        raise ValueError(f'{len(gts)} images of boxes for {len(proposals)} images of proposals')
+    last = nums[-1]
+    props, boxes, p_cnt, g_cnt = [], [], [], []
+    for i, (g, p) in enumerate(zip(gts, proposals)):
+        p = np.asarray(p)
+        if p.ndim == 2 and p.shape[1] == 5:
+            if np.isnan(p[:, 4]).any():
+                raise ValueError(f'image {i}: a proposal score is NaN (it has no place in the evaluation order)')
+            p = p[np.argsort(-p[:, 4], kind='stable')]
+        elif p.size == 0:
+            p = np.zeros((0, 4), np.float32)
+        elif p.ndim != 2 or p.shape[1] != 4:
+            raise ValueError(f'image {i}: proposals of shape {p.shape}, expected [n, 5] or [n, 4]')
+        p = p[:last, :4].astype(np.float32)
+        g = np.zeros((0, 4), np.float32) if g is None else np.asarray(g).astype(np.float32).reshape(-1, 4)
+        if not (np.isfinite(p).all() and np.isfinite(g).all()):
+            raise ValueError(f'image {i}: a box or proposal coordinate is not finite')
+        props.append(p)
+        boxes.append(g)
+        p_cnt.append(len(p))
+        g_cnt.append(len(g))
+    cat = lambda xs: np.concatenate(xs + [np.zeros((0, 4), np.float32)])            # noqa: E731
+    off = lambda c: np.concatenate([[0], np.cumsum(c, dtype=np.int64)]).astype(np.int32)           # noqa: E731
+    assert sum(p_cnt) < 2 ** 31 and sum(g_cnt) < 2 ** 31
+    return dict(props=_aligned16(cat(props)), prop_off=off(p_cnt), gts=_aligned16(cat(boxes)), gt_off=off(g_cnt),
+                nums=np.array([min(v, last) for v in nums], dtype=np.int32))
+
+
+def recall_ious_host(pack, use_legacy_coordinate=False):
+    """recall.py:17-34, the inner loop of ``_recalls`` over ``bbox_overlaps_voc``, for every image and budget of a pack ->
+    fp32 [K, G]: row k, slice gt_off[i] .. gt_off[i + 1] holds ``gt_ious`` of image i IN ROUND ORDER (round j: the largest
+    entry of the matrix - numpy's argmax: the lowest column per box, then the lowest box -, whose row and column become -1;
+    -1 itself once the columns have run out; 0 for every box of an image without a proposal)"""
+    props, p_off, gts, g_off, nums = (pack[k] for k in ('props', 'prop_off', 'gts', 'gt_off', 'nums'))
+    out = np.zeros((len(nums), len(gts)), dtype=np.float32)
+    for i in range(len(g_off) - 1):
+        g0, g1 = g_off[i], g_off[i + 1]
+        if g1 == g0:
+            continue
+        all_ious = bbox_overlaps_voc(gts[g0:g1], props[p_off[i]:p_off[i + 1]], use_legacy_coordinate)
+        for k, proposal_num in enumerate(nums):
+            ious = all_ious[:, :proposal_num].copy()
+            gt_ious = np.zeros((ious.shape[0]))
+            if ious.size == 0:
+                continue
+            for j in range(ious.shape[0]):
+                gt_max_overlaps = ious.argmax(axis=1)
+                max_ious = ious[np.arange(0, ious.shape[0]), gt_max_overlaps]
+                gt_idx = max_ious.argmax()
+                gt_ious[j] = max_ious[gt_idx]
+                box_idx = gt_max_overlaps[gt_idx]
+                ious[gt_idx, :] = -1
+                ious[:, box_idx] = -1
+            out[k, g0:g1] = gt_ious
+    return out
+
+
+def recall_ious_device(pack, use_legacy_coordinate, device, timings=None):
+    """the same IoUs from csrc/recall.hip: one upload of the pack through the staging path, ONE launch for the split and all
+    budgets, one download (``oadg_recall.ious_device``, the module next to the package's import shim that holds the ctypes
+    call of the kernel; see its docstring for why that call is not in hip_ops.py)."""
+    import oadg_recall
+    return oadg_recall.ious_device(pack, pack['nums'], use_legacy_coordinate, device, timings=timings)
+
+
+def recalls_from_ious(ious, iou_thrs):
+    """recall.py:36-41: ``ious`` fp32 [K, G] (any order within a row) -> float64 [K, n_thrs], the fraction of the G boxes whose
+    matched IoU - promoted to fp64 - is >= the fp64 threshold; nan everywhere when there is no box at all (0 / 0.0)"""
+    ious = np.asarray(ious, dtype=np.float32)
+    thrs = np.asarray(iou_thrs, dtype=np.float64).reshape(-1)
+    total_gt_num = ious.shape[1]
+    _ious = np.fliplr(np.sort(ious, axis=1)).astype(np.float64)
+    recalls = np.zeros((ious.shape[0], thrs.size))
+    with np.errstate(divide='ignore', invalid='ignore'):
+        for i, thr in enumerate(thrs):
+            recalls[:, i] = (_ious >= np.float64(thr)).sum(axis=1) / np.float64(total_gt_num)
+    return recalls
+
+
+def _print_log(msg, logger=None):
+    """mmcv.utils.print_log: None prints, 'silent' does not, a logging.Logger logs at INFO"""
+    if logger is None:
+        print(msg)
+    elif logger != 'silent':
+        logger.info(msg)
+
+
+def print_recall_summary(recalls, proposal_nums, iou_thrs, row_idxs=None, col_idxs=None, logger=None):
+    """recall.py:117-147 as a plain text table (one row per budget, one column per threshold, 3 decimals) -> the text"""
+    proposal_nums = np.asarray(proposal_nums, dtype=np.int32).reshape(-1)
+    iou_thrs = np.asarray(iou_thrs).reshape(-1)
+    row_idxs = np.arange(proposal_nums.size) if row_idxs is None else np.asarray(row_idxs)
+    col_idxs = np.arange(iou_thrs.size) if col_idxs is None else np.asarray(col_idxs)
+    rows = [[''] + [str(t) for t in iou_thrs[col_idxs].tolist()]]
+    for i, num in enumerate(proposal_nums[row_idxs]):
+        rows.append([str(int(num))] + [f'{val:.3f}' for val in np.asarray(recalls)[row_idxs[i], col_idxs].tolist()])
+    width = [max(len(r[c]) for r in rows) for c in range(len(rows[0]))]
+    rule = '+' + '+'.join('-' * (w + 2) for w in width) + '+'
+    lines = [rule]
+    for k, r in enumerate(rows):
+        lines.append('| ' + ' | '.join(v.ljust(w) for v, w in zip(r, width)) + ' |')
+        if k == 0:
+            lines.append(rule)
+    lines.append(rule)
+    text = '\n'.join(lines)
+    _print_log('\n' + text, logger=logger)
+    return text
+
+
+def eval_recalls(gts, proposals, proposal_nums=None, iou_thrs=0.5, logger=None, use_legacy_coordinate=False, device=None):
+    """recall.py:65-114 ``eval_recalls``: float64 [n_nums, n_thrs].  gts: per image [g, 4] or None; proposals: per image
+    [n, 5] or [n, 4]; ``proposal_nums``: an int or a sequence of them (the last one also cuts the proposals, as there);
+    ``iou_thrs``: None (0.5), a float or a sequence.  ``device=None``: the host loop (``recall_ious_host``); a torch device:
+    csrc/recall.hip - the same matched IoUs, so the same numbers."""
+    if proposal_nums is None:
+        raise TypeError('eval_recalls needs proposal_nums (an int or a sequence of ints)')
+    nums = [proposal_nums] if isinstance(proposal_nums, (int, np.integer)) else list(np.asarray(proposal_nums).reshape(-1))
+    thrs = np.array([0.5]) if iou_thrs is None else np.asarray(iou_thrs, dtype=np.float64).reshape(-1)
+    pack = pack_recall(gts, proposals, nums)
+    if device is None:
+        ious = recall_ious_host(pack, use_legacy_coordinate)
+    else:
+        ious = recall_ious_device(pack, use_legacy_coordinate, device)
+    recalls = recalls_from_ious(ious, thrs)
+    print_recall_summary(recalls, nums, thrs, logger=logger)
+    return recalls
+
+
+def coco_recall_boxes(ds):
+    """coco.py:313-329: per image the boxes ``fast_eval_recall`` counts - every annotation of the image that is neither a
+    crowd nor marked ``ignore``, whatever its category, x y w h -> x1 y1 x2 y2 in fp32; a synthetic dataset: its boxes"""
+    out = []
+    for i in range(len(ds)):
+        if hasattr(ds, 'coco'):
+            anns = ds.coco.load_anns(ds.coco.get_ann_ids(img_ids=[ds.data_infos[i]['id']]))
+            b = [[a['bbox'][0], a['bbox'][1], a['bbox'][0] + a['bbox'][2], a['bbox'][1] + a['bbox'][3]] for a in anns
+                 if not (a.get('ignore', False) or a.get('iscrowd', 0))]
+            out.append(np.array(b, dtype=np.float32).reshape(-1, 4))
+        else:
+            out.append(np.asarray(ds.boxes(i)[0], dtype=np.float32).reshape(-1, 4))
+    return out
+
+
+def fast_eval_recall(ds, results, proposal_nums, iou_thrs, logger=None, device='auto'):
+    """coco.py:312-334 ``CocoDataset.fast_eval_recall``: the mean over ``iou_thrs`` of ``eval_recalls`` (modern extents)
+    against ``coco_recall_boxes`` -> float64 [n_nums]"""
+    dev = voc_device() if device == 'auto' else device
+    recalls = eval_recalls(coco_recall_boxes(ds), results, proposal_nums, iou_thrs, logger=logger, device=dev)
+    return recalls.mean(axis=1)
+
+
+PROPOSAL_METRICS = ('proposal', 'proposal_fast', 'recall')
+
+
+def _proposal_arrays(results, metric):
+    """results of an RPN run: one [n, 5] (or [n, 4]) array per image"""
+    for i, r in enumerate(results):
+        if isinstance(r, (list, tuple)):
+            raise TypeError(f"metric '{metric}' takes one [n, 5] array of proposals per image (the results of an RPN "
+                            f"detector); image {i} holds a per-class {type(r).__name__} of {len(r)} arrays - those are "
+                            f"detections: use metric 'proposal' (COCO style, class-agnostic) for them")
+    return [np.asarray(r) for r in results]
+
+
+def proposal_evaluate(ds, results, metric, logger=None, device='auto', proposal_nums=(100, 300, 1000), iou_thrs=None,
+                      iou_thr=0.5, metric_items=None):
+    """The three metrics of the reference's ``dataset.evaluate`` that score PROPOSALS -> its flat ordered dict.
+
+    'proposal_fast' (coco.py:426-435; COCO-format and synthetic datasets): ``AR@{num}`` per budget, unrounded floats, the mean
+      over ``iou_thrs`` (default IOU_THRS) of ``eval_recalls``; results: one [n, 5] array per image.
+    'recall' (sdgod.py:90-105 - legacy "+ 1" extents for SdgodDataset -, custom.py:359-369 - modern - for XMLDataset and the
+      synthetic set): ``recall@{num}@{thr}`` per pair and, with more than one ``iou_thr``, ``AR@{num}``; boxes are
+      ``get_ann_info(i)['bboxes']``; results: one array per image.
+    'proposal' (coco.py:437-511: COCOeval with useCats = 0; COCO-format and synthetic datasets): per image all boxes are one
+      category and all detections one list - a per-class result concatenated in class order, or an [n, 5] array -, ordered
+      by ``pack_coco_segments``' stable sort and cut to the last budget; ``AR@100, AR@300, AR@1000, AR_s@1000, AR_m@1000,
+      AR_l@1000`` (or ``metric_items``) as floats of 3 decimals - the names belong to POSITIONS of the summary, as in the
+      reference: with other ``proposal_nums`` 'AR@100' is the recall at proposal_nums[0].
+    ``device``: 'auto' matches on the current GPU when the library and a GPU are present (``voc_device``), None on the host -
+    the same numbers either way."""
+    if not isinstance(metric, str):
+        assert len(metric) == 1, 'one metric'
+        metric = metric[0]
+    if metric not in PROPOSAL_METRICS:
+        raise KeyError(f'metric {metric} is not a proposal metric {PROPOSAL_METRICS}')
+    if len(results) != len(ds):
+        raise ValueError(f'{len(results)} results for {len(ds)} images')
+    voc_style = any(p is VOC_EVAL for p in getattr(type(ds), 'EVAL_PROTOCOLS', ()))
+    coco_style = any(p is COCO_EVAL for p in getattr(type(ds), 'EVAL_PROTOCOLS', ()))
+    if (metric == 'recall' and not voc_style) or (metric != 'recall' and not coco_style):
+        raise KeyError(f'metric {metric} is not supported by {type(ds).__name__}')
+    dev = voc_device() if device == 'auto' else device
+    nums = [int(v) for v in proposal_nums]
+    out = {}          # (insertion-ordered)
+    if metric == 'proposal_fast':
+        thrs = IOU_THRS if iou_thrs is None else iou_thrs
+        ar = fast_eval_recall(ds, _proposal_arrays(results, metric), nums, thrs, logger='silent', device=dev)
+        for i, num in enumerate(nums):
+            out[f'AR@{num}'] = float(ar[i])
+        _print_log(''.join(f'\nAR@{num}\t{ar[i]:.4f}' for i, num in enumerate(nums)), logger=logger)
+    elif metric == 'recall':
+        thrs = [iou_thr] if isinstance(iou_thr, float) else list(iou_thr)
+        boxes = [a['bboxes'] for a in dataset_ann_infos(ds)]
+        legacy = bool(getattr(type(ds), 'RECALL_LEGACY_COORDINATE', False))     # (SdgodDataset: sdgod.py:98; custom.py: modern)
+        recalls = eval_recalls(boxes, _proposal_arrays(results, metric), nums, thrs, logger=logger,
+                               use_legacy_coordinate=legacy, device=dev)
+        for i, num in enumerate(nums):
+            for j, t in enumerate(thrs):
+                out[f'recall@{num}@{t}'] = float(recalls[i, j])
+        if recalls.shape[1] > 1:
+            ar = recalls.mean(axis=1)
+            for i, num in enumerate(nums):
+                out[f'AR@{num}'] = float(ar[i])
+    else:
+        if iou_thrs is not None and not np.array_equal(np.asarray(iou_thrs, dtype=np.float64), IOU_THRS):
+            raise NotImplementedError("evaluation key 'iou_thrs' of metric 'proposal' is not built: the COCO accumulation "
+                                      "here runs at IOU_THRS (.50:.05:.95)")
+        if len(nums) != 3:
+            raise ValueError(f"metric 'proposal' takes three proposal_nums (COCOeval's maxDets), got {nums}")
+        items = MMDET_METRICS[6:] if metric_items is None else \
+            ([metric_items] if isinstance(metric_items, str) else list(metric_items))
+        for it in items:
+            if it not in MMDET_METRICS:
+                raise KeyError(f'metric item {it} is not supported')
+        one_class = [[np.concatenate([np.asarray(c, np.float64).reshape(-1, 5) for c in r]) if isinstance(r, (list, tuple))
+                      else np.asarray(r, np.float64).reshape(-1, 5)] for r in results]
+        gt = [[dict(g, category=0) for g in per_img] for per_img in dataset_gt_anns(ds)]
+        stats = coco_eval_bbox(gt, one_class, 1, max_dets=nums, names=MMDET_METRICS, device=dev)
+        for it in items:
+            out[it] = float(f'{stats[it]:.3f}')
+    return out
+
+
 # ------------------------------------------------------------------------------------------ dataset.evaluate
 # What ``dataset.evaluate(results, metric=..., **eval_kwargs)`` of the reference takes per protocol, and what of it this
 # build computes.  A metric or keyword of the reference that is not built is rejected BY NAME (NotImplementedError), one the
@@ -883,8 +1140,10 @@ def check_evaluate_args(cls, metrics, eval_kwargs):
     for m in metrics:
         if not any(m in p['metrics'] for p in protos):
             if any(m in p['absent'] for p in protos):
+                where = f"; evaluation.proposal_evaluate(dataset, results, '{m}') and tools/test.py --eval {m} compute it" \
+                    if m in PROPOSAL_METRICS else ''
                 raise NotImplementedError(f"metric '{m}' of {cls.__name__}.evaluate is not built "
-                                          f"(built: {[x for p in protos for x in p['metrics']]})")
+                                          f"(built: {[x for p in protos for x in p['metrics']]}){where}")
             raise KeyError(f'metric {m} is not supported by {cls.__name__}')
     used = [p for p in protos if any(m in p['metrics'] for m in metrics)]
     for k in eval_kwargs:

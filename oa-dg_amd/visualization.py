@@ -104,6 +104,16 @@ def det_items(result, class_names, score_thr=0.3, bbox_color=(72, 101, 241), tex
     return _boxes_to_rows(bboxes, labels.tolist(), texts, bbox_color, text_color, thickness, font_size)
 
 
+PROPOSAL_TOP_K = 20                    # RPN.show_result's default (rpn.py:142)
+
+
+def proposal_items(proposals, top_k=PROPOSAL_TOP_K, **style):
+    """one image's proposals (the [n, 5] array an RPN detector returns, best first) -> (items, text bytes): the first
+    ``top_k`` of them (all when top_k <= 0) as the detections of ONE class named 'proposal', with no score threshold"""
+    proposals = np.asarray(proposals, dtype=np.float32).reshape(-1, 5)
+    return det_items([proposals[:top_k] if top_k > 0 else proposals], ('proposal',), 0, **style)
+
+
 def gt_items(bboxes, labels, class_names, color=(0, 255, 0), thickness=2, font_size=13):
     """ground truth ``[k, 4]`` boxes and labels -> (items, text bytes): outline plus class name, the label geometry of
     ``det_items``"""
@@ -131,7 +141,8 @@ def draw_detections(imgs_u8, results, class_names, score_thr=0.3, **style):
     """a painted COPY of the resident uint8 batch [n, H, W, 3]: image i with the detections ``results[i]`` on it"""
     import oadg_draw
     drawn = imgs_u8.contiguous().clone()
-    items, item_off, text = join_lists([det_items(r, class_names, score_thr, **style) for r in results])
+    items, item_off, text = join_lists([proposal_items(r, **style) if isinstance(r, np.ndarray) else
+                                        det_items(r, class_names, score_thr, **style) for r in results])
     return oadg_draw.draw_items(drawn, items, item_off, text)
 
 

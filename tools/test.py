@@ -9,6 +9,14 @@ collects one ``list[np.ndarray [k, 5]]`` (per class) per image, the format ``--o
 ``--eval bbox`` reports the COCO-style numbers the reference's Cityscapes / COCO datasets report (AP@[.50:.95], AP50,
 AP75, APs/m/l, AR...: oadg_amd/evaluation.py, a restatement of pycocotools' COCOeval, which this image does not have);
 ``--eval mAP`` the VOC-style AP@0.5 of mmdet/core/evaluation/mean_ap.py ``eval_map`` (area mode).
+``--eval proposal | proposal_fast | recall [--eval-options k=v ...]`` score PROPOSALS (an 'RPN' detector, configs/rpn/, returns
+one [n, 5] array per image; 'proposal' also takes detections) through ``evaluation.proposal_evaluate``: AR@100 / 300 / 1000 ...
+as ``CocoDataset.evaluate`` reports them, recall@num@thr as the VOC-style datasets do - matched on the GPU (csrc/recall.hip).
+With a proposal metric ``cfg.data.test`` may be a LIST of splits (configs/rpn/rpn_r101_dc5_1x_dwd_sdgod_test.py: the five
+Diverse-Weather domains): the model is built once, every split is tested and scored in turn ('split <i>: ...', its dict; ``--out
+X.pkl`` writes X_<i>.pkl, ``eval.json`` holds the list of dicts), then one line holds the recall at the largest budget per split
+(AR@num with several ``iou_thr``, else recall@num@thr) and its mean.  The detection metrics of a list of splits are
+tools/test_dwd.py's.
 """
 import argparse
 import os
@@ -20,7 +28,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from train import DictAction  # noqa: E402
-from oadg_amd.evaluation import average_precision, eval_map, evaluate  # noqa: E402,F401  (the metric functions live there)
+from oadg_amd.evaluation import (PROPOSAL_METRICS, average_precision, eval_map, evaluate,  # noqa: E402,F401
+                                 proposal_evaluate)                  # (the metric functions live there)
 
 
 def parse_args():
@@ -29,7 +38,11 @@ def parse_args():
     p.add_argument('checkpoint', help="checkpoint file ('none' = random init, for smoke runs)")
     p.add_argument('--work-dir', help='the directory to save the evaluation metrics')
     p.add_argument('--out', help='output result file in pickle format')
-    p.add_argument('--eval', type=str, nargs='+', help="evaluation metrics: 'bbox' (COCO style), 'mAP' (VOC style AP@0.5)")
+    p.add_argument('--eval', type=str, nargs='+',
+                   help="evaluation metrics: 'bbox' (COCO style), 'mAP' (VOC style AP@0.5); for proposals 'proposal', "
+                        "'proposal_fast' (COCO style) or 'recall' (VOC style)")
+    p.add_argument('--eval-options', nargs='+', action=DictAction,
+                   help="keywords of the proposal metrics, key=value: proposal_nums, iou_thrs, iou_thr, metric_items")
     p.add_argument('--cfg-options', nargs='+', action=DictAction, help='override config entries, key=value')
     p.add_argument('--launcher', choices=['none', 'pytorch', 'slurm', 'mpi'], default='none')
     p.add_argument('--local_rank', type=int, default=0)
@@ -94,6 +107,82 @@ def run_test(model, data_cfg, dev, amp, samples_per_gpu=1, max_samples=None, sho
     return results, ds, time.time() - t0
 
 
+def count_rows(results):
+    """'<k> detections' for per-class results, '<k> proposals' for the one-array-per-image results of an RPN detector"""
+    if results and all(hasattr(r, 'shape') for r in results):
+        return f'{sum(len(r) for r in results)} proposals'
+    return f'{sum(len(r) if hasattr(r, "shape") else sum(len(c) for c in r) for r in results)} detections'
+
+
+def _dwd_tool():
+    """tools/test_dwd.py by path: the home of ``first_images`` (--max-samples: what was tested is what is scored) and of
+    ``_literal`` (--eval-options values as Python literals) - one copy of each, used by both tools"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('oadg_tools_test_dwd',
+                                                  os.path.join(os.path.dirname(os.path.abspath(__file__)), 'test_dwd.py'))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def score_proposals(ds, results, metric, eval_options):
+    """``proposal_evaluate`` on the images that were tested (the first len(results) of ``ds``).  A ConcatDataset is scored as
+    ``ConcatDataset.evaluate`` scores it - every dataset on its own slice of the results, keys prefixed ``{k}_`` - except that
+    a concatenation of ONE dataset (a one-entry ``ann_file`` list) keeps that dataset's plain keys."""
+    D = _dwd_tool()
+    kw = {k: D._literal(v) for k, v in (eval_options or {}).items()}
+    ds = D.first_images(ds, len(results))
+    parts = [d for d in ds.datasets if len(d)] if hasattr(ds, 'datasets') else [ds]
+    if len(parts) == 1:
+        return proposal_evaluate(parts[0], results, metric, logger='silent', **kw)
+    out, start = {}, 0
+    for k, d in enumerate(parts):
+        for name, v in proposal_evaluate(d, results[start:start + len(d)], metric, logger='silent', **kw).items():
+            out[f'{k}_{name}'] = v
+        start += len(d)
+    return out
+
+
+def check_splits_arguments(a, n_splits):
+    """what tools/test.py does with a list of splits, checked before the model is built"""
+    if not a.eval or len(a.eval) != 1 or a.eval[0] not in PROPOSAL_METRICS:
+        raise NotImplementedError(f'cfg.data.test is a list of {n_splits} splits: tools/test.py walks it for one proposal '
+                                  f'metric (--eval {" | ".join(PROPOSAL_METRICS)}); the detection metrics of a list of '
+                                  f'splits are tools/test_dwd.py\'s')
+    if a.out:
+        assert a.out.endswith(('.pkl', '.pickle')), 'The output file must be a pkl file.'
+
+
+def test_splits(a, cfg, model, dev, amp):
+    """``cfg.data.test`` as a list of splits, for ONE proposal metric: every split tested and scored in turn, then a line with
+    the recall at the largest budget per split and its mean"""
+    import json
+    metric, dicts = a.eval[0], []
+    for i, dcfg in enumerate(cfg.data.test):
+        show_dir = os.path.join(a.show_dir, f'split_{i}') if a.show_dir else None
+        results, ds, dt = run_test(model, dcfg, dev, amp, cfg.data.get('samples_per_gpu', 1), a.max_samples,
+                                   show_dir=show_dir, show_score_thr=a.show_score_thr)
+        n = len(results)
+        print(f'split {i}: {n} images in {dt:.2f} s ({n / dt:.1f} img/s), {count_rows(results)}')
+        if a.out:
+            root, ext = os.path.splitext(a.out)
+            path = f'{root}_{i}{ext}'
+            with open(path, 'wb') as f:
+                pickle.dump(results, f)
+            print(f'writing results to {path}')
+        dicts.append(score_proposals(ds, results, metric, a.eval_options))
+        print(f'{metric}: {dicts[-1]}')
+        if a.work_dir:
+            os.makedirs(a.work_dir, exist_ok=True)
+            with open(os.path.join(a.work_dir, 'eval.json'), 'w') as f:
+                json.dump({metric: dicts}, f, indent=1)
+    # the recall at the largest budget: AR@num over several thresholds, recall@num@thr with a single one
+    keys = [k for k in dicts[0] if k.startswith('AR@')] or [k for k in dicts[0] if k.startswith('recall@')]
+    if keys:
+        vals = [d[keys[-1]] for d in dicts]
+        print(f'{keys[-1]} per split: ' + ' '.join(f'{v:.3f}' for v in vals) + f'  mean {sum(vals) / len(vals):.3f}')
+
+
 def main():
     a = parse_args()
     from oadg_amd import Config
@@ -103,21 +192,30 @@ def main():
     torch.cuda.set_device(int(os.environ.get('LOCAL_RANK', 0)) % torch.cuda.device_count())
     dev = torch.device('cuda', torch.cuda.current_device())
     amp = torch.bfloat16 if a.amp == 'bf16' else None
+    if isinstance(cfg.data.test, (list, tuple)):
+        check_splits_arguments(a, len(cfg.data.test))
     model = build_model(cfg, a.checkpoint, dev, amp, a.allow_partial_checkpoint)
     dcfg = cfg.data.test
+    if isinstance(dcfg, (list, tuple)):
+        return test_splits(a, cfg, model, dev, amp)
     results, ds, dt = run_test(model, dcfg, dev, amp, cfg.data.get('samples_per_gpu', 1), a.max_samples,
                                show_dir=a.show_dir, show_score_thr=a.show_score_thr)
     n = len(results)
-    print(f'{n} images in {dt:.2f} s ({n / dt:.1f} img/s), {sum(len(c) for r in results for c in r)} detections')
+    print(f'{n} images in {dt:.2f} s ({n / dt:.1f} img/s), {count_rows(results)}')
     if a.out:
         assert a.out.endswith(('.pkl', '.pickle')), 'The output file must be a pkl file.'
         with open(a.out, 'wb') as f:
             pickle.dump(results, f)
         print(f'writing results to {a.out}')
     if a.eval:
-        assert set(a.eval) <= {'bbox', 'mAP'}, "--eval bbox (COCO style) and / or mAP (VOC style AP@0.5)"
+        assert set(a.eval) <= {'bbox', 'mAP'} | set(PROPOSAL_METRICS), \
+            "--eval bbox (COCO style), mAP (VOC style AP@0.5), proposal / proposal_fast / recall (proposals)"
         nc = len(getattr(ds, 'CLASSES', None) or range(dcfg.get('num_classes', 8)))
-        ev = evaluate(results, ds, a.eval, nc, mmdet_style=True)
+        ev = evaluate(results, ds, [m for m in a.eval if m not in PROPOSAL_METRICS], nc, mmdet_style=True)
+        for m in a.eval:
+            if m in PROPOSAL_METRICS:
+                ev[m] = score_proposals(ds, results, m, a.eval_options)
+                print(f'{m}: {ev[m]}')                      # (the reference's dict, floats at full precision)
         if 'bbox' in ev:
             print('bbox (COCO style): ' + '  '.join(f'{k} {v:.3f}' for k, v in ev['bbox'].items()))
         if 'mAP' in ev:
@@ -127,7 +225,7 @@ def main():
             import json
             os.makedirs(a.work_dir, exist_ok=True)
             with open(os.path.join(a.work_dir, 'eval.json'), 'w') as f:
-                json.dump({k: (v if k == 'bbox' else dict(mAP=v['mAP'], per_class=list(v['per_class'])))
+                json.dump({k: (dict(mAP=v['mAP'], per_class=list(v['per_class'])) if k == 'mAP' else v)
                            for k, v in ev.items()}, f, indent=1)
 
 
