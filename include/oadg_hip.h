@@ -403,6 +403,39 @@ int oadg_coco_match(const double* dets, const int32_t* det_off, const double* gt
                     int32_t* match, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * COCO error analysis: the plain and the two "ignore confusion" matchings of a test split (csrc/coco_error.hip)
+ *   replaces tools/analysis_tools/coco_error_analysis.py analyze_results / analyze_individual_category: one COCOeval at IoU
+ *            0.75 / 0.5 / 0.1 and, per class, two COCOevals at IoU 0.1 on a deep copy of the dataset whose boxes of the other
+ *            classes (of the same supercategory / of any class) are relabelled ignore = 1, iscrowd = 1, category_id = catId -
+ *            1 + 2 K evaluations of the split, K-fold copies of every box - as evaluation.coco_error_flags_host restates them
+ * A segment is one (image, category) pair, s = image * num_classes + category, n_img * num_classes of them (< 2^31).  dets,
+ * det_off [n_img * num_classes + 1]: as oadg_coco_match.  gts: fp64 [n_gt][4] = x, y, w, h, ALL boxes of image i at
+ * gts[img_off[i] .. img_off[i+1]) in annotation order, stored once; gt_area fp64 [n_gt], gt_crowd uint8 [n_gt], gt_cat int32
+ * [n_gt] (a box whose category is outside [0, num_classes) takes no part); img_off: int32 [n_img + 1]; cat_super: int32
+ * [num_classes], equal numbers = one supercategory.  Offsets are clamped to the arrays' extents before use.
+ * iou_thrs_host: n_thr (>= 0) thresholds, area_rng_host: n_area pairs lo, hi, in HOST memory (read during the call);
+ * (n_thr + 2) * n_area <= OADG_COCO_MAX_LANES, OADG_EARG otherwise.  Rows per area range, matched as oadg_coco_match matches:
+ *   rows 0 .. n_thr-1: the boxes of the segment's own category, at iou_thrs_host[t];
+ *   row n_thr:         also the boxes of the other categories of the same supercategory, at sim_thr;
+ *   row n_thr + 1:     also the boxes of every other category, at sim_thr.
+ * A foreign box is a crowd there: IoU = intersection / the detection's area, always ignored, never taken.
+ *   flags [n_area][n_thr + 2][n_det] uint8: 0 false positive, 1 true positive, 2 ignored, as oadg_coco_match.
+ * Every element that belongs to a detection of a segment is written; the same bytes from run to run.  Images of up to
+ * OADG_COCO_ERROR_LDS_GTS boxes are staged once; larger ones in chunks of that size with their taken words in the workspace,
+ * detections OADG_COCO_ERROR_LDS_DETS at a time.  The workspace (8-byte aligned, contents irrelevant) must hold
+ * oadg_coco_error_workspace_bytes(...) bytes (0: arguments the call refuses); OADG_ESIZE when it is smaller; OADG_EARG for
+ * null or misaligned pointers.  One launch, no allocation, no synchronisation.  Called from oadg_coco_error.py only (the device
+ * half of evaluation.coco_error_analysis(device=...)). */
+#define OADG_COCO_ERROR_LDS_GTS 256
+#define OADG_COCO_ERROR_LDS_DETS 64
+size_t oadg_coco_error_workspace_bytes(int n_img, int num_classes, int n_det, int n_gt, int n_thr, int n_area);
+int oadg_coco_error_match(const double* dets, const int32_t* det_off, const double* gts, const double* gt_area,
+                          const uint8_t* gt_crowd, const int32_t* gt_cat, const int32_t* img_off, const int32_t* cat_super,
+                          int n_img, int num_classes, int n_det, int n_gt, const double* iou_thrs_host, int n_thr,
+                          double sim_thr, const double* area_rng_host, int n_area, uint8_t* flags, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Confusion counts of a test split (csrc/confusion.hip)
  *   replaces tools/analysis_tools/confusion_matrix.py:95-142 analyze_per_img_dets + bbox_overlaps.py, one Python triple
  *   loop (classes x detections x boxes) per image

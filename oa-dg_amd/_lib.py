@@ -65,6 +65,7 @@ RPN_MAX_LEVELS = 8
 PARSE_LOSSES_MAX = 32
 VOC_MAX_THRS = 8
 COCO_MAX_LANES, COCO_LDS_GTS, COCO_LDS_DETS = 64, 128, 64   # csrc/coco_eval.hip: matchings of one call, staging capacities
+COCO_ERROR_LDS_GTS, COCO_ERROR_LDS_DETS = 256, 64           # csrc/coco_error.hip: boxes of an image / detections staged at once
 # csrc/confusion.hip: boxes staged per pass, boxes whose "found" words fit in LDS, (C + 1)^2 cells counted in LDS, largest C
 CONFUSION_CHUNK, CONFUSION_LDS_BOXES, CONFUSION_LDS_CELLS, CONFUSION_MAX_CLASSES = 128, 512, 8192, 4096
 # csrc/recall.hip: proposals of an (image, budget) staged in LDS, boxes whose matching state fits in LDS, budgets of one call
@@ -257,6 +258,9 @@ SIGNATURES = {
     'oadg_voc_tpfp': (ci, [vp, vp, vp, vp, vp, ci, ci, ci, POINTER(cf), ci, ci, vp, vp, vp, vp, cs, vp]),
     'oadg_coco_match_workspace_bytes': (cs, [ci, ci, ci, ci, ci]),
     'oadg_coco_match': (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, POINTER(cd), ci, POINTER(cd), ci, vp, vp, vp, cs, vp]),
+    'oadg_coco_error_workspace_bytes': (cs, [ci, ci, ci, ci, ci, ci]),
+    'oadg_coco_error_match': (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, POINTER(cd), ci, cd, POINTER(cd), ci, vp, vp, cs,
+                                   vp]),
     'oadg_confusion_workspace_bytes': (cs, [ci, ci, ci, ci]),
     'oadg_confusion_count': (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, vp, vp, cs, vp]),
     'oadg_recall_match_workspace_bytes': (cs, [ci, ci, ci, ci]),

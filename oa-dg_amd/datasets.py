@@ -148,6 +148,44 @@ class CocoDataset:
         """coco.py:364-573 for 'bbox' (XMLDataset: voc.py:28-106 for 'mAP'): evaluation.dataset_evaluate"""
         return evaluation.dataset_evaluate(self, results, metric=metric, logger=logger, **eval_kwargs)
 
+    # ---- coco.py:182-362, detections only (no masks here; proposals are scored by evaluation.proposal_evaluate)
+    @staticmethod
+    def xyxy2xywh(bbox):
+        """one result row -> [x, y, w, h] as Python floats (the subtraction happens in double, on the row's own values)"""
+        b = bbox.tolist()
+        return [b[0], b[1], b[2] - b[0], b[3] - b[1]]
+
+    def _det2json(self, results):
+        """per image a list of [k, 5] arrays per class -> the records of a COCO result file, image after image, class after
+        class, row after row"""
+        return [dict(image_id=self.img_ids[idx], bbox=self.xyxy2xywh(row), score=float(row[4]), category_id=self.cat_ids[label])
+                for idx in range(len(self)) for label, rows in enumerate(results[idx]) for row in rows]
+
+    def results2json(self, results, outfile_prefix):
+        """writes ``<outfile_prefix>.bbox.json`` -> dict(bbox=..., proposal=...) (both name that file, as in the reference)"""
+        if results and not isinstance(results[0], list):
+            raise TypeError('invalid type of results: format_results writes detections, a list of [k, 5] arrays per image '
+                            '(masks and the one-array-per-image results of an RPN detector are not built)')
+        path = f'{outfile_prefix}.bbox.json'
+        if os.path.dirname(path):
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, 'w') as f:
+            json.dump(self._det2json(results), f)
+        return dict(bbox=path, proposal=path)
+
+    def format_results(self, results, jsonfile_prefix=None, **kwargs):
+        """-> (result_files, tmp_dir): the json file of ``results2json`` under ``jsonfile_prefix`` ('a/b/prefix'), or in a
+        ``tempfile.TemporaryDirectory`` - returned, the caller cleans it up - when there is no prefix"""
+        assert isinstance(results, list), 'results must be a list'
+        assert len(results) == len(self), \
+            'The length of results is not equal to the dataset len: {} != {}'.format(len(results), len(self))
+        tmp_dir = None
+        if jsonfile_prefix is None:
+            import tempfile
+            tmp_dir = tempfile.TemporaryDirectory()
+            jsonfile_prefix = os.path.join(tmp_dir.name, 'results')
+        return self.results2json(results, jsonfile_prefix), tmp_dir
+
     def fast_eval_recall(self, results, proposal_nums, iou_thrs, logger=None, device='auto'):
         """coco.py:312-334: per budget the recall of one [n, 5] array of proposals per image, averaged over ``iou_thrs``
         (evaluation.fast_eval_recall; matched on the GPU when there is one)"""
@@ -338,6 +376,11 @@ class XMLDataset(CocoDataset):
 
     def evaluate(self, results, metric='mAP', logger=None, **eval_kwargs):
         return evaluation.dataset_evaluate(self, results, metric=metric, logger=logger, **eval_kwargs)
+
+    def format_results(self, results, **kwargs):
+        """custom.py:185-186 of the reference is an empty placeholder: a VOC-style dataset has no result file"""
+        raise NotImplementedError(f'{type(self).__name__}.format_results is not built: the COCO result file belongs to the '
+                                  f'COCO-format datasets (CocoDataset, CityscapesDataset)')
 
     def __init__(self, min_size=None, img_subdir='JPEGImages', ann_subdir='Annotations', **kwargs):
         assert self.CLASSES or kwargs.get('classes', None), 'CLASSES in `XMLDataset` can not be None.'

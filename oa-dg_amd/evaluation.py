@@ -49,11 +49,12 @@ def _iou_xywh(d, g, iscrowd):
     return np.where(union > 0, out, 0.0)
 
 
-def _evaluate_img(gts, dts, a_rng, max_det):
+def _evaluate_img(gts, dts, a_rng, max_det, iou_thrs=None):
     """COCOeval.evaluateImg for one (image, category).  gts: list of dict(bbox xywh, area, iscrowd); dts: list of
-    dict(bbox xywh, area, score).  Returns None when both are empty."""
+    dict(bbox xywh, area, score).  Returns None when both are empty.  ``iou_thrs``: params.iouThrs, IOU_THRS by default."""
     if not gts and not dts:
         return None
+    iou_thrs = IOU_THRS if iou_thrs is None else iou_thrs
     g_ig = np.array([1 if (g['iscrowd'] or g['area'] < a_rng[0] or g['area'] > a_rng[1]) else 0 for g in gts], int)
     gtind = np.argsort(g_ig, kind='mergesort')
     gts = [gts[i] for i in gtind]
@@ -62,10 +63,10 @@ def _evaluate_img(gts, dts, a_rng, max_det):
     dts = [dts[i] for i in dtind]
     iscrowd = [int(g['iscrowd']) for g in gts]
     ious = _iou_xywh([d['bbox'] for d in dts], [g['bbox'] for g in gts], iscrowd)
-    T, G, D = len(IOU_THRS), len(gts), len(dts)
+    T, G, D = len(iou_thrs), len(gts), len(dts)
     gtm, dtm, dt_ig = np.zeros((T, G)), np.zeros((T, D)), np.zeros((T, D))
     if G and D:
-        for ti, t in enumerate(IOU_THRS):
+        for ti, t in enumerate(iou_thrs):
             for di in range(D):
                 iou, m = min(t, 1 - 1e-10), -1
                 for gi in range(G):
@@ -177,11 +178,12 @@ def coco_summarize(precision, recall, names=None):
 COCO_FP, COCO_TP, COCO_IGNORED = 0, 1, 2
 
 
-def pack_coco_segments(gt_anns, results, num_classes, max_det):
+def pack_coco_segments(gt_anns, results, num_classes, max_det, xywh=False):
     """a split as the arrays of oadg_coco_match: one segment per (image, category), s = image * num_classes + category.
     dict(dets fp64 [D, 4] = x, y, w, h - per segment by descending score (stable) and cut to ``max_det`` -, det_off int32
     [S + 1], gts fp64 [G, 4] = x, y, w, h in annotation order, gt_area fp64 [G] (the annotation's field), gt_crowd uint8 [G],
-    gt_off int32 [S + 1]; per kept detection det_score fp64, det_rank (its place within the segment) and det_cat; gt_cat)"""
+    gt_off int32 [S + 1]; per kept detection det_score fp64, det_rank (its place within the segment) and det_cat; gt_cat).
+    ``xywh``: the rows of ``results`` are x, y, w, h, score already (a COCO result file read back: nothing is subtracted)."""
     n, K = len(gt_anns), int(num_classes)
     assert len(results) == n
     S = n * K
@@ -196,7 +198,10 @@ def pack_coco_segments(gt_anns, results, num_classes, max_det):
     keep = rank < max_det
     d, seg, rank = d[keep], seg[keep], rank[keep]
     # CocoDataset._det2json / xyxy2xywh
-    dets = np.stack([d[:, 0], d[:, 1], d[:, 2] - d[:, 0], d[:, 3] - d[:, 1]], axis=1) if len(d) else np.zeros((0, 4))
+    if xywh:
+        dets = d[:, :4]
+    else:
+        dets = np.stack([d[:, 0], d[:, 1], d[:, 2] - d[:, 0], d[:, 3] - d[:, 1]], axis=1) if len(d) else np.zeros((0, 4))
     anns = [(i, g) for i, per_img in enumerate(gt_anns) for g in per_img]
     g_img = np.fromiter((i for i, _ in anns), dtype=np.int64, count=len(anns))
     g_cat = np.fromiter((g['category'] for _, g in anns), dtype=np.int64, count=len(anns))
@@ -215,14 +220,16 @@ def pack_coco_segments(gt_anns, results, num_classes, max_det):
                 num_classes=K)
 
 
-def coco_flags_host(pack, thrs=None, area_rng=None, want_match=False):
+def coco_flags_host(pack, thrs=None, area_rng=None, want_match=False, iou_thrs=None):
     """``_evaluate_img`` over every (segment, area range) of a pack -> flags uint8 [n_area, n_thr, D]: COCO_FP (unmatched,
     inside the range), COCO_TP (matched to a box that is not ignored), COCO_IGNORED (matched to an ignored box, or unmatched
     and outside the range); with ``want_match`` also int32 [n_area, n_thr, D], the matched box within its segment in
-    annotation order, or -1.  ``thrs``: thresholds out of IOU_THRS (``_evaluate_img`` knows no others), all of them by default."""
-    thrs = IOU_THRS if thrs is None else thrs
+    annotation order, or -1.  ``thrs``: thresholds out of IOU_THRS (``_evaluate_img`` knows no others), all of them by default.
+    ``iou_thrs``: another params.iouThrs for ``_evaluate_img`` to match at, in the place of IOU_THRS in the sentence before."""
+    iou_thrs = IOU_THRS if iou_thrs is None else np.asarray(iou_thrs, np.float64)
+    thrs = iou_thrs if thrs is None else thrs
     area_rng = AREA_RNG if area_rng is None else area_rng
-    rows = [np.flatnonzero(IOU_THRS == t) for t in thrs]
+    rows = [np.flatnonzero(iou_thrs == t) for t in thrs]
     if any(len(r) != 1 for r in rows):
         raise ValueError('the host evaluator matches at IOU_THRS only')
     rows = np.concatenate(rows) if rows else np.zeros(0, np.int64)
@@ -236,7 +243,7 @@ def coco_flags_host(pack, thrs=None, area_rng=None, want_match=False):
         dts = [dict(bbox=pack['dets'][j], area=pack['dets'][j, 2] * pack['dets'][j, 3], score=pack['det_score'][j])
                for j in range(d0, d1)]
         for a, a_rng in enumerate(area_rng):
-            e = _evaluate_img(gts, dts, a_rng, d1 - d0)
+            e = _evaluate_img(gts, dts, a_rng, d1 - d0, iou_thrs)
             dtm, dt_ig = e['dtm'][rows], e['dt_ig'][rows]
             flags[a, :, d0:d1] = np.where(dt_ig, COCO_IGNORED, np.where(dtm > 0, COCO_TP, COCO_FP))
             if want_match and g1 > g0:
@@ -256,19 +263,24 @@ def coco_flags_device(pack, thrs, area_rng, device, timings=None, want_match=Fal
     return oadg_coco_match.flags_device(pack, thrs, area_rng, device, timings=timings, want_match=want_match)
 
 
-def coco_accumulate(pack, flags, max_dets):
+def coco_accumulate(pack, flags, max_dets, iou_thrs=None, area_rng=None):
     """COCOeval.accumulate over the flags of a pack (uint8 [A, T, D] for AREA_RNG and IOU_THRS, in pack order) -> (precision
     [T, R, K, A, M], recall [T, K, A, M]), exactly the arrays ``coco_eval_bbox`` fills: per (category, area range, maxDets)
     the detections of rank < maxDets by descending score (stable over the images in order), fp64 cumulative tp / fp,
-    recall over the boxes that are not ignored, the precision envelope sampled at REC_THRS; -1 where no box counts."""
-    T, R, K, A, M = len(IOU_THRS), len(REC_THRS), pack['num_classes'], len(AREA_RNG), len(max_dets)
+    recall over the boxes that are not ignored, the precision envelope sampled at REC_THRS; -1 where no box counts.
+    ``iou_thrs`` / ``area_rng``: the thresholds (only their number is read) and area ranges of ``flags`` when they are not
+    IOU_THRS and AREA_RNG.  The boxes that count are those of ``gt_cat``'s own class (pack_coco_error: the relabelled boxes of
+    the two variants are ignored, so they never count)."""
+    iou_thrs = IOU_THRS if iou_thrs is None else iou_thrs
+    area_rng = AREA_RNG if area_rng is None else area_rng
+    T, R, K, A, M = len(iou_thrs), len(REC_THRS), pack['num_classes'], len(area_rng), len(max_dets)
     assert flags.shape == (A, T, len(pack['dets']))
     precision = -np.ones((T, R, K, A, M))
     recall = -np.ones((T, K, A, M))
     eps = np.spacing(1)
     area, crowd = pack['gt_area'], pack['gt_crowd'] != 0
     # the boxes that count per (category, area range): not crowd, area inside [lo, hi]
-    npig = np.stack([np.bincount(pack['gt_cat'][~(crowd | (area < lo) | (area > hi))], minlength=K) for lo, hi in AREA_RNG], 1)
+    npig = np.stack([np.bincount(pack['gt_cat'][~(crowd | (area < lo) | (area > hi))], minlength=K) for lo, hi in area_rng], 1)
     score, rank, cat = pack['det_score'], pack['det_rank'], pack['det_cat']
     by_cat = np.argsort(cat, kind='stable')
     cuts = np.searchsorted(cat[by_cat], np.arange(K + 1))
@@ -297,6 +309,135 @@ def coco_accumulate(pack, flags, max_dets):
                     q[t, ok] = pr[t, pi[ok]]
                 precision[:, :, k, a, m] = q
     return precision, recall
+
+
+# ------------------------------------------------------------------------------------------ COCO error analysis
+# tools/analysis_tools/coco_error_analysis.py of the reference: the precision lost by each class split into C75 / C50 (AP at
+# IoU 0.75 / 0.5), Loc (AP at 0.1), Sim (AP at 0.1 when confusion inside the supercategory is ignored), Oth (when confusion with
+# every class is ignored), BG and FN.  The reference runs COCOeval once at [0.75, 0.5, 0.1] and per class twice more at [0.1]
+# on a deep copy of the dataset whose foreign boxes are relabelled `ignore = 1, iscrowd = 1, category_id = catId`.  Here: one
+# pack that holds every box of an image once, all 3 + 2 matchings x 4 area ranges of every (image, class) in one launch of
+# csrc/coco_error.hip (or the literal host restatement below, the yardstick), one accumulate.
+ERROR_THRS = (0.75, 0.5, 0.1)              # analyze_results: cocoEval.params.iouThrs
+ERROR_SIM_THR = 0.1                        # analyze_individual_category: cocoEval.params.iouThrs of both variants
+ERROR_TYPES = ('C75', 'C50', 'Loc', 'Sim', 'Oth', 'BG', 'FN')
+ERROR_AREA_NAMES = ('allarea', 'small', 'medium', 'large')
+ERROR_MAX_DET = 100
+
+
+def error_area_rng(areas):
+    """analyze_results: the three ``--areas`` bounds as params.areaRng (all, small, medium, large)"""
+    areas = list(areas)
+    assert len(areas) == 3, '3 integers should be specified as areas, representing 3 area regions'
+    return [[0 ** 2, areas[2]], [0 ** 2, areas[0]], [areas[0], areas[1]], [areas[1], areas[2]]]
+
+
+def pack_error_boxes(gt_anns, num_classes, supercats):
+    """the box half of ``pack_coco_error``: every box of an image ONCE, whatever its class - gts fp64 [G, 4] = x, y, w, h in
+    annotation order, gt_area, gt_crowd uint8, gt_cat int32, img_off int32 [n + 1] - and cat_super int32 [K] from ``supercats``
+    (one hashable per class, equal values = one supercategory)"""
+    n, K = len(gt_anns), int(num_classes)
+    assert len(supercats) == K and n * K < 2 ** 31
+    anns = [(i, g) for i, per_img in enumerate(gt_anns) for g in per_img if 0 <= g['category'] < K]
+    G = len(anns)
+    assert G < 2 ** 31
+    g_img = np.fromiter((i for i, _ in anns), dtype=np.int64, count=G)
+    ids = {}
+    cat_super = np.array([ids.setdefault(v, len(ids)) for v in supercats], np.int32).reshape(K)
+    return dict(gts=np.ascontiguousarray(np.array([g['bbox'] for _, g in anns], np.float64).reshape(-1, 4)),
+                gt_area=np.fromiter((g['area'] for _, g in anns), dtype=np.float64, count=G),
+                gt_crowd=np.fromiter((bool(g['iscrowd']) for _, g in anns), dtype=np.uint8, count=G),
+                gt_cat=np.fromiter((g['category'] for _, g in anns), dtype=np.int32, count=G),
+                img_off=np.concatenate([[0], np.cumsum(np.bincount(g_img, minlength=n))]).astype(np.int32),
+                cat_super=cat_super, num_classes=K)
+
+
+def pack_coco_error(gt_anns, results, num_classes, supercats, max_det=ERROR_MAX_DET, xywh=False):
+    """a split as the arrays of oadg_coco_error_match.  The detections as ``pack_coco_segments`` packs them (dets, det_off,
+    det_score, det_rank, det_cat: one segment per (image, category), s = image * num_classes + category, by descending score,
+    cut to ``max_det``; ``xywh`` as there); the boxes as ``pack_error_boxes`` packs them, once per image."""
+    seg = pack_coco_segments([[] for _ in range(len(gt_anns))], results, int(num_classes), max_det, xywh=xywh)
+    return dict(pack_error_boxes(gt_anns, num_classes, supercats),
+                **{k: seg[k] for k in ('dets', 'det_off', 'det_score', 'det_rank', 'det_cat')})
+
+
+def coco_error_flags_host(pack, thrs, sim_thr, area_rng):
+    """the yardstick of csrc/coco_error.hip -> flags uint8 [n_area, n_thr + 2, D].  Per (image, category k) segment with
+    detections the reference's three box lists, built literally: the boxes of class k for the plain rows; for row n_thr the
+    annotations of the image in order, those of another class of k's supercategory relabelled iscrowd = 1 (pycocotools derives
+    ``ignore`` from it) and category k, the rest of the foreign ones left out; for row n_thr + 1 every foreign one relabelled.
+    Each list goes through ``_evaluate_img`` at its own thresholds."""
+    K, D = pack['num_classes'], len(pack['dets'])
+    thrs = [float(t) for t in thrs]
+    T = len(thrs)
+    flags = np.zeros((len(area_rng), T + 2, D), dtype=np.uint8)
+    d_off, i_off, sup = pack['det_off'], pack['img_off'], pack['cat_super']
+    for s in np.flatnonzero(np.diff(d_off)):
+        i, k = divmod(int(s), K)
+        d0, d1 = d_off[s], d_off[s + 1]
+        anns = [dict(bbox=pack['gts'][g], area=pack['gt_area'][g], iscrowd=int(pack['gt_crowd'][g]), category=int(pack['gt_cat'][g]))
+                for g in range(i_off[i], i_off[i + 1])]
+        dts = [dict(bbox=pack['dets'][j], area=pack['dets'][j, 2] * pack['dets'][j, 3], score=pack['det_score'][j])
+               for j in range(d0, d1)]
+
+        def relabelled(foreign):
+            out = []
+            for ann in anns:
+                ann = dict(ann)                                      # (copy.deepcopy(cocoGt))
+                if ann['category'] != k and foreign(ann['category']):
+                    ann.update(ignore=1, iscrowd=1, category=k)
+                if ann['category'] == k:                             # (useCats = 1: _gts[imgId, catId])
+                    out.append(ann)
+            return out
+        lists = [(relabelled(lambda c: False), thrs, slice(0, T)),
+                 (relabelled(lambda c: sup[c] == sup[k]), [float(sim_thr)], slice(T, T + 1)),
+                 (relabelled(lambda c: True), [float(sim_thr)], slice(T + 1, T + 2))]
+        for gts, iou_thrs, rows in lists:
+            if not iou_thrs:
+                continue
+            for a, a_rng in enumerate(area_rng):
+                e = _evaluate_img(gts, dts, a_rng, d1 - d0, iou_thrs)
+                flags[a, rows, d0:d1] = np.where(e['dt_ig'], COCO_IGNORED, np.where(e['dtm'] > 0, COCO_TP, COCO_FP))
+    return flags
+
+
+def coco_error_flags_device(pack, thrs, sim_thr, area_rng, device, timings=None):
+    """the same flags from csrc/coco_error.hip: one upload of the pack through the staging path, ONE launch for the split, all
+    rows and all area ranges, one download (``oadg_coco_error.flags_device``, the module next to the package's import shim that
+    holds the ctypes call of the kernel; see its docstring for why that call is not in hip_ops.py)."""
+    import oadg_coco_error
+    return oadg_coco_error.flags_device(pack, thrs, sim_thr, area_rng, device, timings=timings)
+
+
+def coco_error_analysis(gt_anns, results, num_classes, supercats, areas=(1024, 9216, 10 ** 10), device=None, timings=None,
+                        xywh=False):
+    """analyze_results of the reference's coco_error_analysis.py for 'bbox' -> ps fp64 [7, R, K, 4, 1], the array it plots:
+    the precision at the 101 recall thresholds per (ERROR_TYPES band, class, area range), maxDets = 100.  Bands 0 - 2 are the
+    plain evaluation at ERROR_THRS, 3 and 4 the two variants at ERROR_SIM_THR, then ``ps[ps == -1] = 0``, BG = (Oth > 0),
+    FN = 1.  gt_anns / results: as ``coco_eval_bbox`` (``xywh``: as ``pack_coco_segments``); supercats: one value per class.  ``device=None``: the host yardstick;
+    a torch device: one launch of csrc/coco_error.hip - the same flags, so the same array."""
+    area_rng = error_area_rng(areas)
+    pack = pack_coco_error(gt_anns, results, num_classes, supercats, xywh=xywh)
+    if device is None:
+        flags = coco_error_flags_host(pack, ERROR_THRS, ERROR_SIM_THR, area_rng)
+    else:
+        flags = coco_error_flags_device(pack, ERROR_THRS, ERROR_SIM_THR, area_rng, device, timings=timings)
+    rows = list(ERROR_THRS) + [ERROR_SIM_THR] * 2
+    precision, _ = coco_accumulate(pack, flags, [ERROR_MAX_DET], iou_thrs=rows, area_rng=area_rng)
+    ps = np.vstack([precision, np.zeros((2, *precision.shape[1:]))])
+    ps[ps == -1] = 0
+    ps[5] = ps[4] > 0
+    ps[6] = 1.0
+    return ps
+
+
+def error_band_means(ps, names):
+    """the numbers of the plots' legends, unrounded: per class (and 'allclass') and per area range the mean of each band"""
+    out = {}
+    for name, sub in list(zip(names, np.moveaxis(ps, 2, 0))) + [('allclass', ps)]:
+        out[name] = {area: {t: float(sub[b][..., a, 0].mean()) for b, t in enumerate(ERROR_TYPES)}
+                     for a, area in enumerate(ERROR_AREA_NAMES)}
+    return out
 
 
 def dataset_gt_anns(dataset, indices=None):

@@ -17,6 +17,8 @@ Diverse-Weather domains): the model is built once, every split is tested and sco
 X.pkl`` writes X_<i>.pkl, ``eval.json`` holds the list of dicts), then one line holds the recall at the largest budget per split
 (AR@num with several ``iou_thr``, else recall@num@thr) and its mean.  The detection metrics of a list of splits are
 tools/test_dwd.py's.
+``--format-only [--eval-options jsonfile_prefix=P]`` writes the detections as a COCO result file, ``P.bbox.json``
+(``CocoDataset.format_results``: what tools/analysis_tools/coco_error_analysis.py reads), and evaluates nothing.
 """
 import argparse
 import os
@@ -38,11 +40,15 @@ def parse_args():
     p.add_argument('checkpoint', help="checkpoint file ('none' = random init, for smoke runs)")
     p.add_argument('--work-dir', help='the directory to save the evaluation metrics')
     p.add_argument('--out', help='output result file in pickle format')
+    p.add_argument('--format-only', action='store_true',
+                   help='write the detections as a COCO result file (--eval-options jsonfile_prefix=P -> P.bbox.json) without '
+                        'evaluating them')
     p.add_argument('--eval', type=str, nargs='+',
                    help="evaluation metrics: 'bbox' (COCO style), 'mAP' (VOC style AP@0.5); for proposals 'proposal', "
                         "'proposal_fast' (COCO style) or 'recall' (VOC style)")
     p.add_argument('--eval-options', nargs='+', action=DictAction,
-                   help="keywords of the proposal metrics, key=value: proposal_nums, iou_thrs, iou_thr, metric_items")
+                   help="keywords of the proposal metrics, key=value: proposal_nums, iou_thrs, iou_thr, metric_items; with "
+                        "--format-only: jsonfile_prefix")
     p.add_argument('--cfg-options', nargs='+', action=DictAction, help='override config entries, key=value')
     p.add_argument('--launcher', choices=['none', 'pytorch', 'slurm', 'mpi'], default='none')
     p.add_argument('--local_rank', type=int, default=0)
@@ -54,6 +60,8 @@ def parse_args():
     a = p.parse_args()
     os.environ.setdefault('LOCAL_RANK', str(a.local_rank))
     check_show_arguments(a)
+    if a.eval and a.format_only:
+        raise ValueError('--eval and --format_only cannot be both specified')
     return a
 
 
@@ -114,6 +122,22 @@ def count_rows(results):
     return f'{sum(len(r) if hasattr(r, "shape") else sum(len(c) for c in r) for r in results)} detections'
 
 
+def format_only(ds, results, eval_options):
+    """tools/test.py:263-264 of the reference: ``dataset.format_results(outputs, **eval_options)`` on the images that were
+    tested -> the files it wrote.  Without ``jsonfile_prefix`` the file lives in a temporary directory that goes with this
+    call, as in the reference: name a prefix to keep it."""
+    D = _dwd_tool()
+    if not hasattr(ds, 'format_results'):
+        raise NotImplementedError(f'--format-only: {type(ds).__name__} has no format_results()')
+    files, tmp_dir = D.first_images(ds, len(results)).format_results(
+        results, **{k: D._literal(v) for k, v in (eval_options or {}).items()})
+    print(f'writing results to {files["bbox"]}' + (' (a temporary directory: pass --eval-options jsonfile_prefix=P to keep it)'
+                                                   if tmp_dir is not None else ''))
+    if tmp_dir is not None:
+        tmp_dir.cleanup()
+    return files
+
+
 def _dwd_tool():
     """tools/test_dwd.py by path: the home of ``first_images`` (--max-samples: what was tested is what is scored) and of
     ``_literal`` (--eval-options values as Python literals) - one copy of each, used by both tools"""
@@ -145,6 +169,9 @@ def score_proposals(ds, results, metric, eval_options):
 
 def check_splits_arguments(a, n_splits):
     """what tools/test.py does with a list of splits, checked before the model is built"""
+    if a.format_only:
+        raise NotImplementedError(f'--format-only: cfg.data.test is a list of {n_splits} splits and a COCO result file holds one '
+                                  f'split; name one split with --cfg-options')
     if not a.eval or len(a.eval) != 1 or a.eval[0] not in PROPOSAL_METRICS:
         raise NotImplementedError(f'cfg.data.test is a list of {n_splits} splits: tools/test.py walks it for one proposal '
                                   f'metric (--eval {" | ".join(PROPOSAL_METRICS)}); the detection metrics of a list of '
@@ -202,11 +229,18 @@ def main():
                                show_dir=a.show_dir, show_score_thr=a.show_score_thr)
     n = len(results)
     print(f'{n} images in {dt:.2f} s ({n / dt:.1f} img/s), {count_rows(results)}')
+    return report(a, results, ds, dcfg)
+
+
+def report(a, results, ds, dcfg):
+    """what follows the test of one split: --out, then --format-only (nothing is evaluated) or --eval"""
     if a.out:
         assert a.out.endswith(('.pkl', '.pickle')), 'The output file must be a pkl file.'
         with open(a.out, 'wb') as f:
             pickle.dump(results, f)
         print(f'writing results to {a.out}')
+    if a.format_only:
+        return format_only(ds, results, a.eval_options)
     if a.eval:
         assert set(a.eval) <= {'bbox', 'mAP'} | set(PROPOSAL_METRICS), \
             "--eval bbox (COCO style), mAP (VOC style AP@0.5), proposal / proposal_fast / recall (proposals)"
