@@ -315,8 +315,11 @@ int oadg_oamix_normalize(const uint8_t* img, int H, int W, const float* mean_hos
  *                        colour, BGR byte order)
  * PNG file -> uint8 [H][W][3] in B, G, R order at `out` (any host memory: the data set hands in a slice of a pinned
  * batch buffer) - zlib inflate + the five PNG row filters, one call without the interpreter lock.  8-bit grey / RGB / RGBA,
- * non-interlaced; OADG_EUNSUPPORTED for any other PNG variant (the caller decodes those with PIL), OADG_ESIZE when the
- * file's extent is not H x W, OADG_EIO when it cannot be read.  oadg_png_size: the extent from the header.
+ * non-interlaced; OADG_EUNSUPPORTED for any other PNG variant and for a malformed file (a filter byte above 4, IDAT chunks
+ * that do not follow one another, data short of the image, a damaged zlib stream: the caller decodes those with PIL, so
+ * the error is PIL's), OADG_ESIZE when the file's extent is not H x W, OADG_EIO when it cannot be read.  Nothing outside
+ * `out` is written whatever the file holds; OADG_OK only with the bytes PIL decodes.  oadg_png_size: the extent from the
+ * header.
  *   oadg_png_decode_gray16  mmcv.imread(inst_file, 'unchanged')  tools/dataset_converters/cityscapes.py:42
  * 16-bit (or 8-bit, widened) greyscale, non-interlaced PNG -> native uint16 [H][W] at `out`; the same return codes. */
 int oadg_png_size(const char* path, int* height, int* width);
@@ -558,9 +561,11 @@ int oadg_draw_items_u8(uint8_t* imgs, int n, int H, int W, const int32_t* items,
  *             BGR byte order; libjpeg-turbo's defaults: islow IDCT, fancy upsampling)
  * Byte-equal to PIL / OpenCV.  Covers SOF0 / SOF1, 8-bit, Huffman, one scan holding every component, 8- or 16-bit DQT,
  * restart intervals; grey, or YCbCr with luma sampling 1x1 / 2x1 / 2x2 and chroma 1x1.  Any other variant (progressive,
- * arithmetic, lossless, 12-bit, multi-scan, CMYK, RGB-coded, other sampling, DNL) returns OADG_EUNSUPPORTED and a truncated
- * or corrupt stream OADG_EFORMAT: the caller decodes that file with PIL.  OADG_ESIZE when the file's extent is not H x W,
- * OADG_EIO when it cannot be read.
+ * arithmetic, lossless, 12-bit, multi-scan, CMYK, RGB-coded, other sampling, DNL, coefficients so large that libjpeg-turbo's
+ * own IDCT forms disagree) returns OADG_EUNSUPPORTED and a truncated or corrupt stream (bad tables, lengths, markers, restart
+ * order, codes; the list is in csrc/jpeg_decode.hip) OADG_EFORMAT: the caller decodes that file with PIL.  OADG_ESIZE when
+ * the file's extent is not H x W, OADG_EIO when it cannot be read.  The files are untrusted: no byte outside the file and
+ * the caller's buffers is read or written whatever they hold, and OADG_OK comes only with the bytes PIL decodes.
  *
  * oadg_jpeg_desc: what the pixel stage needs of one image.  Each component's coefficients cover its MCU-padded block grid
  * (bw x bh blocks, row-major), starting `off` int16 elements into the image's slot; each block holds its 64 QUANTIZED

@@ -13,8 +13,29 @@
 // Covered: SOF0 / SOF1, 8-bit, Huffman, one scan holding every component, 8- or 16-bit DQT, DRI / RSTn, byte stuffing and
 // fill bytes, grey or YCbCr with luma sampling 1x1, 2x1 or 2x2 and chroma 1x1.  Everything else returns OADG_EUNSUPPORTED
 // (the caller decodes that file with PIL); a truncated or corrupt stream returns OADG_EFORMAT (the caller hands the file to
-// PIL, so the error users see is PIL's).  So does a block whose dequantized coefficient leaves int16 (only pathological
-// streams: libjpeg-turbo's SIMD and C paths disagree there, so there is no single target to match).
+// PIL, so the error users see is PIL's).
+// The rule for untrusted bytes: OADG_OK only for a file PIL loads, with PIL's bytes; no read or write outside the file
+// and the caller's buffers whatever the bytes are.  Where in doubt the file is rejected - stricter than libjpeg is fine,
+// laxer is not.  What tests/jpeg_cases.py + tests/test_decoder_robustness.py pin (PIL the judge of every file):
+//   decoded: fill bytes before any marker (RSTn and EOI too), bytes after EOI, COM / APPn (an APP1 holding a whole JPEG:
+//     the size is the outer frame's), tables packed in one segment or one each, defined twice (the last definition
+//     holds), placed after SOF, in unused slots, a 16-bit DQT under SOF0, DRI given twice / 0 / beyond the MCU count,
+//     grey files with any sampling factors (ignored: one block per MCU), and the colour space as libjpeg infers it
+//     (jdapimin.c default_decompress_parms): JFIF wins over an Adobe marker and over component ids, Adobe transform 1 and
+//     ids 1,2,3 without JFIF are YCbCr
+//   declined (OADG_EUNSUPPORTED): ids 'R','G','B' or Adobe transform 0 without JFIF (RGB-coded), 12-bit, every frame type
+//     but SOF0 / SOF1, height 0 / DNL, 4:4:0 and any chroma factor but 1x1, 4 components, a second scan, and a block
+//     where libjpeg-turbo's C and SIMD IDCT forms would disagree (idct_forms_agree below: only pathological streams)
+//   rejected: a Huffman table with more codes of a length than the length holds or an all-ones code (checked before any
+//     lookup entry is written), wrong Tc / Th / Tq / Pq, DC symbols above 15, segment lengths that are short, long (SOF,
+//     SOS and DRI lengths must be exact, as in libjpeg) or past the end of the file, a second SOF, SOS before SOF or
+//     with other components, ids or tables than the frame defined, spectral selection other than 0 / 63 / 0, restart
+//     markers out of order, missing, surplus or without DRI, codes no table assigns, AC runs past coefficient 63, DC
+//     categories above 11, data or EOI missing, anything but FF after SOI (PIL knows a JPEG by FF D8 FF) and segments
+//     under a reserved marker code (TEM, 02 .. BF, JPGn, DHP, EXP: libjpeg and PIL stop there)
+//   swept: every prefix of a file is rejected; every header byte set to 00, FF, b ^ 01, b ^ 80 and 1500 files of
+//     extreme coefficients either decode to PIL's bytes or are rejected.
+// make -C oa-dg_amd/csrc decoder-asan runs the host stage over all of them under AddressSanitizer + UBSan.
 // The IDCT, upsampling and colour functions are __host__ __device__: oadg_jpeg_decode_bgr runs the same source on the host.
 #include <limits.h>
 #include <stdio.h>
@@ -270,6 +291,9 @@ int build_huff(Huff& t, const uint8_t* counts, const uint8_t* vals, int nvals, b
     int code = 0, k = 0;
     for (int l = 1; l <= 16; ++l) {
         const int n = counts[l - 1];
+        // more codes than the length holds (or one of all ones): checked BEFORE the lookup entries of this length are
+        // written - an oversubscribed length would index past fast[]
+        if (code + n >= (1 << l)) return OADG_EFORMAT;
         t.maxcode[l] = n ? code + n - 1 : -1;
         t.delta[l] = k - code;
         for (int i = 0; i < n; ++i, ++code, ++k) {
@@ -277,7 +301,6 @@ int build_huff(Huff& t, const uint8_t* counts, const uint8_t* vals, int nvals, b
             if (l <= 9)
                 for (int j = 0; j < (1 << (9 - l)); ++j) t.fast[(code << (9 - l)) | j] = (uint16_t)((l << 8) | vals[k]);
         }
-        if (code >= (1 << l)) return OADG_EFORMAT;
         code <<= 1;
     }
     t.maxcode[17] = INT_MAX;
@@ -330,7 +353,7 @@ inline int extend(int v, int s) { return v < (1 << (s - 1)) ? v - (1 << s) + 1 :
 
 // one block: zero it, DC difference + AC run/size codes in zig-zag order, stored column-major.  The dequantized value of
 // every coefficient must stay within int16 (see the file comment).
-inline int decode_block(Bits& b, const Huff& dc, const Huff& ac, int& pred, int16_t* blk, const uint16_t* q) {
+inline int decode_block(Bits& b, const Huff& dc, const Huff& ac, int& pred, int16_t* blk, const uint16_t* q, long& mag) {
     memset(blk, 0, 64 * sizeof(int16_t));
     b.fill();
     int s = huff_decode(b, dc);
@@ -339,6 +362,7 @@ inline int decode_block(Bits& b, const Huff& dc, const Huff& ac, int& pred, int1
     if (pred < -32768 || pred > 32767) return OADG_EFORMAT;
     if ((long)(pred < 0 ? -pred : pred) * q[0] > 32767) return OADG_EUNSUPPORTED;
     blk[0] = (int16_t)pred;
+    mag = (long)(pred < 0 ? -pred : pred) * q[0];
     for (int k = 1; k < 64;) {
         if (b.n < 32) b.fill();
         const int rs = huff_decode(b, ac);
@@ -350,7 +374,9 @@ inline int decode_block(Bits& b, const Huff& dc, const Huff& ac, int& pred, int1
             if (k > 63 || s > 10) return OADG_EFORMAT;
             const int v = extend(b.get(s), s);
             const int pos = kZz.idx[k];
-            if ((long)(v < 0 ? -v : v) * q[pos] > 32767) return OADG_EUNSUPPORTED;
+            const long a = (long)(v < 0 ? -v : v) * q[pos];
+            if (a > 32767) return OADG_EUNSUPPORTED;
+            mag += a;
             blk[pos] = (int16_t)v;
             ++k;
         } else {
@@ -359,6 +385,42 @@ inline int decode_block(Bits& b, const Huff& dc, const Huff& ac, int& pred, int1
         }
     }
     return OADG_OK;
+}
+
+// libjpeg-turbo decodes a block with the C form of jidctint.c or with a SIMD form of it, and the two agree only while
+// nothing saturates: the SIMD forms add dequantized coefficients and column-pass results in 16-bit lanes and pack the
+// column-pass results and the samples with signed saturation, where the C form keeps ints and wraps the sample through
+// range_limit[v & 1023].  With every dequantized coefficient and every column-pass value within +-16383 (so that no
+// 16-bit sum of two of them wraps and none saturates) and every descaled sample within [-512, 511] (where wrapping and
+// clamping give the same byte) both forms compute what idct_islow computes.  A block outside that is declined.
+// kPlainSum: a block whose dequantized magnitudes sum to S has samples within 0.25 S (a basis function's amplitude is at
+// most cos^2(pi/16) / 4) and column-pass values within 4 * 1.39 S (PASS1_BITS, the largest butterfly gain), so at
+// S <= 2000 it is inside all three bounds with room for the fixed-point rounding and is not looked at further.
+constexpr long kPlainSum = 2000;
+
+bool idct_forms_agree(const int16_t* blk, const uint16_t* q) {
+    int in[64], ws[64], o[8];
+    for (int k = 0; k < 64; ++k) {
+        in[k] = (int)blk[k] * (int)q[k];
+        if (in[k] < -16383 || in[k] > 16383) return false;
+    }
+    for (int u = 0; u < 8; ++u) {
+        const int* c = in + u * 8;
+        idct_1d(c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], o);
+        for (int r = 0; r < 8; ++r) {
+            ws[r * 8 + u] = descale(o[r], kConstBits - kPass1Bits);
+            if (ws[r * 8 + u] < -16383 || ws[r * 8 + u] > 16383) return false;
+        }
+    }
+    for (int r = 0; r < 8; ++r) {
+        const int* w = ws + r * 8;
+        idct_1d(w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], o);
+        for (int x = 0; x < 8; ++x) {
+            const int v = descale(o[x], kConstBits + kPass1Bits + 3);
+            if (v < -512 || v > 511) return false;
+        }
+    }
+    return true;
 }
 
 inline unsigned be16(const uint8_t* p) { return ((unsigned)p[0] << 8) | p[1]; }
@@ -426,7 +488,7 @@ struct Decoder {
         if (W == 0) return OADG_EFORMAT;
         if (H == 0) return OADG_EUNSUPPORTED;             // height given by a DNL marker
         if (nc != 1 && nc != 3) return OADG_EUNSUPPORTED; // CMYK / YCCK, two-component files
-        if (len < 6 + 3 * nc) return OADG_EFORMAT;
+        if (len != 6 + 3 * nc) return OADG_EFORMAT;        // (libjpeg: JERR_BAD_LENGTH for a longer one too)
         for (int i = 0; i < nc; ++i) {
             comp[i].id = s[6 + 3 * i];
             comp[i].h = s[7 + 3 * i] >> 4;
@@ -468,13 +530,20 @@ struct Decoder {
         return OADG_OK;
     }
 
+    // a marker code no segment may start with here.  Below 0xC0 (TEM, the reserved codes, a stuffed zero), JPGn, DHP and EXP
+    // stop libjpeg (jdmarker.c read_markers: JERR_UNKNOWN_MARKER) or PIL's own marker walk ("no marker found"); RSTn and a
+    // second SOI are out of place
+    static bool stray_marker(int m) {
+        return m < 0xC0 || (m >= 0xD0 && m <= 0xD8) || m == 0xDE || m == 0xDF || (m >= 0xF0 && m <= 0xFD);
+    }
+
     // headers up to the frame (for oadg_jpeg_size) or up to the scan
     int headers(bool stop_at_frame, const uint8_t** sos, long* sos_len) {
         if (size < 4 || f[0] != 0xFF || f[1] != 0xD8) return OADG_EUNSUPPORTED;
+        if (f[2] != 0xFF) return OADG_EFORMAT;            // (PIL knows a JPEG by FF D8 FF: garbage right after SOI is no image)
         for (;;) {
             const int m = next_marker();
-            if (m < 0 || m == 0xD9) return OADG_EFORMAT;
-            if (m == 0x01 || (m >= 0xD0 && m <= 0xD8)) return OADG_EFORMAT;
+            if (m < 0 || m == 0xD9 || stray_marker(m)) return OADG_EFORMAT;
             const uint8_t* s;
             long len;
             int rc = segment(&s, &len);
@@ -498,7 +567,7 @@ struct Decoder {
             } else if (m == 0xDB) {
                 if ((rc = parse_dqt(s, len))) return rc;
             } else if (m == 0xDD) {
-                if (len < 2) return OADG_EFORMAT;
+                if (len != 2) return OADG_EFORMAT;
                 restart = (int)be16(s);
             } else if (m == 0xE0) {
                 if (len >= 5 && memcmp(s, "JFIF\0", 5) == 0) jfif = true;
@@ -537,7 +606,7 @@ int entropy_decode(const uint8_t* file, long size, int H, int W, int16_t* coef, 
     // scan header
     if (sos_len < 1) return OADG_EFORMAT;
     const int ns = sos[0];
-    if (sos_len < 4 + 2 * ns || ns < 1 || ns > 4) return OADG_EFORMAT;
+    if (sos_len != 4 + 2 * ns || ns < 1 || ns > 4) return OADG_EFORMAT;      // (libjpeg: the length must be exact)
     if (ns != nc) return OADG_EUNSUPPORTED;               // multi-scan sequential
     for (int i = 0; i < ns; ++i) {
         if (sos[1 + 2 * i] != dec.comp[i].id) return OADG_EUNSUPPORTED;
@@ -611,7 +680,7 @@ int entropy_decode(const uint8_t* file, long size, int H, int W, int16_t* coef, 
     dec.pos = p;
     for (int m = end_marker; rc == OADG_OK && m != 0xD9; m = dec.next_marker()) {
         if (m == 0xDA || m == 0xDC) rc = OADG_EUNSUPPORTED;
-        else if (m < 0 || m == 0x01 || (m >= 0xD0 && m <= 0xD8)) rc = OADG_EFORMAT;
+        else if (m < 0 || Decoder::stray_marker(m)) rc = OADG_EFORMAT;
         else {
             const uint8_t* s;
             long len;
@@ -633,7 +702,9 @@ int entropy_decode(const uint8_t* file, long size, int H, int W, int16_t* coef, 
                     for (int bx = 0; bx < hs[i] && rc == OADG_OK; ++bx) {
                         const long row = my * vs[i] + by, col = mx * hs[i] + bx;
                         int16_t* blk = coef + d->off[i] + (row * d->bw[i] + col) * 64;
-                        rc = decode_block(bits, *dct[i], *act[i], pred[i], blk, d->qt[i]);
+                        long mag;
+                        rc = decode_block(bits, *dct[i], *act[i], pred[i], blk, d->qt[i], mag);
+                        if (rc == OADG_OK && mag > kPlainSum && !idct_forms_agree(blk, d->qt[i])) rc = OADG_EUNSUPPORTED;
                     }
             }
             if (rc == OADG_OK && bits.over > 64) rc = OADG_EFORMAT;     // far past the data

@@ -10,6 +10,15 @@
 // Covers what such datasets hold: 8-bit grey / RGB / RGBA, non-interlaced (oadg_png_decode_gray16: the 16-bit grey instance
 // maps of Cityscapes' gtFine, for tools/dataset_converters/cityscapes.py); anything else returns OADG_EUNSUPPORTED and the
 // caller falls back to PIL.  Host code only (compiled by hipcc with the rest of the library, links zlib).
+// The rule for untrusted bytes is jpeg_decode.hip's: OADG_OK only for a file PIL loads, with PIL's bytes.  Pinned by
+// tests/test_decoder_robustness.py with the writer of tests/jpeg_cases.py (PIL's own encoder never picks Average):
+//   decoded: each of the five filters on every row and on the first row alone at 1, 2 (16-bit grey), 3 and 4 bytes per
+//     pixel, extents down to 1 x 1; IDAT split after every byte, empty IDAT chunks, ancillary chunks (tEXt, gAMA, tRNS)
+//     before the data, scanline data beyond the last row (ignored, as by PIL)
+//   declined (OADG_EUNSUPPORTED): interlaced, palette, depth 1 / 2 / 4, 16-bit RGB, grey with alpha, a filter byte above
+//     4, a chunk between two IDAT chunks (PIL reports such a file truncated), and every malformed file: a chunk length
+//     past the end, data short of the image, IHDR not first, a damaged signature, fewer than 57 bytes, a zlib stream of
+//     garbage.  Chunk CRCs are not checked.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -101,21 +110,27 @@ int inflate_file(const char* path, int H, int W, bool gray16, unsigned char** ra
         zs.avail_out = (uInt)need;
         long pos = 8;
         int zrc = Z_OK;
-        bool end = false;
+        bool end = false, idat_seen = false, idat_closed = false, idat_apart = false;
         while (pos + 12 <= size && !end) {
             const unsigned len = be32(file + pos);
             const unsigned char* type = file + pos + 4;
             if (pos + 12 + (long)len > size) break;
-            if (memcmp(type, "IDAT", 4) == 0 && zrc == Z_OK) {
-                zs.next_in = file + pos + 8;
-                zs.avail_in = len;
-                zrc = inflate(&zs, Z_NO_FLUSH);
-            } else if (memcmp(type, "IEND", 4) == 0) {
-                end = true;
+            if (memcmp(type, "IDAT", 4) == 0) {
+                // the IDAT chunks must follow one another: PIL stops at a chunk between them and reports a truncated file
+                if (idat_closed) { idat_apart = true; break; }
+                idat_seen = true;
+                if (len && zrc == Z_OK) {                  // (an empty IDAT is legal; inflate would answer Z_BUF_ERROR)
+                    zs.next_in = file + pos + 8;
+                    zs.avail_in = len;
+                    zrc = inflate(&zs, Z_NO_FLUSH);
+                }
+            } else {
+                if (idat_seen) idat_closed = true;
+                if (memcmp(type, "IEND", 4) == 0) end = true;
             }
             pos += 12 + (long)len;
         }
-        const bool complete = (zrc == Z_STREAM_END || zrc == Z_OK) && zs.total_out == (uLong)need;
+        const bool complete = !idat_apart && (zrc == Z_STREAM_END || zrc == Z_OK) && zs.total_out == (uLong)need;
         inflateEnd(&zs);
         if (!complete) break;
         *raw_out = raw;

@@ -144,10 +144,30 @@ def test_integrate_data_uses_the_shared_allocation_of_adjacent_views():
     assert torch.equal(out['img'], both)
 
 
+def _png_row_filters(path):
+    """the set of filter bytes of a non-interlaced 8-bit PNG's scanlines"""
+    import struct
+    import zlib
+    raw = open(path, 'rb').read()
+    w, h, depth, ctype = struct.unpack('>IIBB', raw[16:26])
+    pos, idat = 8, b''
+    while pos < len(raw):
+        n, kind = struct.unpack('>I4s', raw[pos:pos + 8])
+        if kind == b'IDAT':
+            idat += raw[pos + 8:pos + 8 + n]
+        pos += 12 + n
+    line = 1 + w * {0: 1, 2: 3, 6: 4}[ctype] * depth // 8
+    lines = zlib.decompress(idat)
+    assert len(lines) == h * line
+    return set(lines[::line])
+
+
 def test_native_png_decoder_equals_pil(tmp_path):
     """csrc/png_decode.hip (host code: zlib inflate + the five PNG row filters, BGR written in place) against PIL on RGB /
-    RGBA / grey files of odd extents, low-pass and noisy content (PIL's encoder picks the row filters adaptively: all five
-    occur), several zlib levels; a 16-bit file is declined (-4: the data set then decodes it with PIL), a wrong extent is
+    RGBA / grey files of odd extents, low-pass and noisy content, several zlib levels.  PIL's encoder picks the row
+    filters adaptively, but never Average: these files hold None, Sub, Up and Paeth rows (read back from their inflated
+    scanlines below).  Every filter at every pixel width, first rows included, is forced by the writer of
+    tests/jpeg_cases.py in tests/test_decoder_robustness.py; a 16-bit file is declined (-4: the data set then decodes it with PIL), a wrong extent is
     -2, a missing file -3; and CocoDataset.decode_into takes the native path for PNG and PIL for everything else."""
     import ctypes
     from PIL import Image
@@ -159,7 +179,7 @@ def test_native_png_decoder_equals_pil(tmp_path):
                                       (129, 255, 'RGB')]):
         ch = {'RGB': 3, 'RGBA': 4, 'L': 1}[mode]
         a = rs.randint(0, 256, (h, w, ch)).astype(np.uint8)
-        if k % 2 == 1:                       # smooth content: Sub / Up / Average / Paeth rows
+        if k % 2 == 1:                       # smooth content: Sub / Up / Paeth rows
             a = (np.cumsum(np.cumsum(a.astype(np.float64), 0), 1) / (np.arange(1, h + 1)[:, None, None] * np.arange(1, w + 1)[None, :, None])).astype(np.uint8)
         img = Image.fromarray(a[:, :, 0] if ch == 1 else a, mode)
         path = str(tmp_path / f'c{k}.png')
@@ -175,6 +195,8 @@ def test_native_png_decoder_equals_pil(tmp_path):
             ref = np.asarray(im.convert('RGB'))[:, :, ::-1]
         assert np.array_equal(out, ref), path
         assert L.oadg_png_decode_bgr(path.encode(), out.ctypes.data, h + 1, w) == -2
+        filters |= _png_row_filters(path)
+    assert filters == {0, 1, 2, 4}, filters
     a16 = (rs.randint(0, 65536, (9, 11)).astype(np.uint16))
     Image.fromarray(a16).save(str(tmp_path / 'deep.png'))
     out = np.zeros((9, 11, 3), np.uint8)

@@ -326,8 +326,8 @@ LAUNCHES_NOTHING = {
 }
 # the data pipeline, OA-Mix, the decoders and the corruptions: they run before an audited step installs anything (or not
 # in it at all) and have byte-exact suites of their own (tests/test_hip_oamix.py, test_oracle_oamix.py,
-# test_oamix_buffers.py, test_oamix_ops.py, test_geometric.py, test_jpeg_decode.py, test_sdgod_dataset.py, test_hip_corrupt.py,
-# test_corrupt.py) - not part of the audited step.  (The fp32 parity convolutions are audited launch by launch in the fp32
+# test_oamix_buffers.py, test_oamix_ops.py, test_geometric.py, test_jpeg_decode.py, test_decoder_robustness.py,
+# test_sdgod_dataset.py, test_hip_corrupt.py, test_corrupt.py) - not part of the audited step.  (The fp32 parity convolutions are audited launch by launch in the fp32
 # step: tests/f32_audit.py)
 OWN_SUITES = {
     'oadg_chamfer_l2_5x5', 'oadg_glass_shuffle_u8', 'oadg_corrupt_correlate1d', 'oadg_corrupt_defocus', 'oadg_corrupt_elastic',
