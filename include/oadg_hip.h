@@ -310,6 +310,43 @@ int oadg_oamix_normalize(const uint8_t* img, int H, int W, const float* mean_hos
                          int to_rgb, void* out, int out_dtype, int Hp, int Wp, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * PhotoMetricDistortion + CutOut + Normalize + Pad for a whole batch in ONE launch (csrc/photo.hip)
+ *   reference: mmdet/datasets/pipelines/transforms.py:941-1041 (PhotoMetricDistortion), :1874-1944 (CutOut),
+ *              :618-629,699-701 (Normalize, Pad); mmcv.bgr2hsv / hsv2bgr = OpenCV's float32 HSV with H in 0..360
+ * table: n_images records in DEVICE memory, one per image; rects: int32 [.][4] = x1, y1, x2, y2 (exclusive; x2 <= x1 or
+ * y2 <= y1: an empty hole) in DEVICE memory, the holes of image i at rects[rect_off .. rect_off + n_rects).  The host only
+ * reads mean_host / stdinv_host.  Image i is written to out + i * out_image_stride_elems elements as [Hp][Wp][3]
+ * (out_image_stride_elems >= Hp * Wp * 3; every H <= Hp and W <= Wp is the CALLER's promise - the table is not read on the
+ * host - and a record that breaks it writes nothing outside its own Hp x Wp x 3 slice: rows / columns beyond are dropped).
+ * Per pixel, all float32, nothing contracted, nothing clamped:
+ *   bytes -> float; [CutOut first: fill inside a hole]; [if OADG_PHOTO_PRESENT: + delta; * alpha_pre; BGR -> HSV (always);
+ *   s * sat; h + hue, then h > 360: h - 360, then h < 0: h + 360; HSV -> BGR (always); * alpha_post; channel c = channel
+ *   perm[c]] - each step only with its flag -; [OADG_PHOTO_CUTOUT_LAST: fill inside a hole]; the BGR -> RGB swap if to_rgb;
+ *   (x - mean[c]) * stdinv[c]; bf16 (round to nearest even) when out_dtype == 1.  y >= H or x >= W: 0.
+ * Without OADG_PHOTO_PRESENT and with fills that are whole numbers the result is bit for bit oadg_oamix_normalize's on the
+ * uint8 image with the holes filled.  The same bytes from run to run. */
+#define OADG_PHOTO_PRESENT 1
+#define OADG_PHOTO_DELTA 2
+#define OADG_PHOTO_ALPHA_PRE 4
+#define OADG_PHOTO_SAT 8
+#define OADG_PHOTO_HUE 16
+#define OADG_PHOTO_ALPHA_POST 32
+#define OADG_PHOTO_PERM 64
+#define OADG_PHOTO_CUTOUT_LAST 128
+typedef struct {
+    const uint8_t* img;        /* uint8 [H][W][3], BGR, dense */
+    int H, W;
+    int flags;                 /* OADG_PHOTO_* */
+    int rect_off, n_rects;     /* this image's holes in rects */
+    int perm[3];               /* output channel c = input channel perm[c] (OADG_PHOTO_PERM) */
+    float delta, alpha_pre, sat, hue, alpha_post;
+    float fill[3];             /* the value of a hole pixel, per (BGR) channel */
+} oadg_photo_image;            /* 72 bytes */
+int oadg_photo_normalize_batch(const oadg_photo_image* table, int n_images, const int32_t* rects, const float* mean_host,
+                               const float* stdinv_host, int to_rgb, void* out, int out_dtype, int Hp, int Wp,
+                               size_t out_image_stride_elems, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Input files (HOST functions, no device work; csrc/png_decode.hip)
  *   oadg_png_decode_bgr  LoadImageFromFile  mmdet/datasets/pipelines/loading.py:33-78 (mmcv.imfrombytes -> cv2.imdecode:
  *                        colour, BGR byte order)

@@ -84,6 +84,10 @@ CORRUPT_TO_U8_CLIP, CORRUPT_TO_U8, CORRUPT_TO_F32 = 0, 1, 2
 CORRUPT_BRIGHTNESS, CORRUPT_SATURATE = 0, 1
 DRAW_OUTLINE, DRAW_FILL, DRAW_TEXT = 0, 1, 2   # kinds of a display-list row (csrc/draw.hip)
 DRAW_ITEM_INTS = 8
+# flag word of an oadg_photo_image (csrc/photo.hip): a photometric step is present at all / which of its sub-steps were drawn /
+# CutOut follows the photometric step (else it precedes it)
+PHOTO_PRESENT, PHOTO_DELTA, PHOTO_ALPHA_PRE, PHOTO_SAT, PHOTO_HUE, PHOTO_ALPHA_POST, PHOTO_PERM, PHOTO_CUTOUT_LAST = (
+    1, 2, 4, 8, 16, 32, 64, 128)
 
 
 # ---- the tables that are filled with numpy: Structure + its record dtype (pointer fields come out as uint64) ----------------
@@ -135,15 +139,21 @@ class JpegDesc(Structure):   # oadg_jpeg_desc (filled by oadg_jpeg_entropy_decod
         [('off', c_int64 * 4), ('qt', c_uint16 * 64 * 4)]
 
 
-COLSUM_JOB, WGRAD_JOB, PREP_BWD_JOB, PREP_DESC, SELECT_JOB, SGD_TENSOR, MIX_TARGET, BBOX_STEP, BBOX_CHAIN = (
-    np.dtype(c) for c in (ColsumJob, WgradJob, PrepBwdJob, PrepDesc, SelectJob, SgdTensor, MixTarget, BboxStep, BboxChain))
+class PhotoImage(Structure):   # oadg_photo_image
+    _fields_ = [('img', vp)] + _f(ci, 'H W flags rect_off n_rects') + [('perm', ci * 3)] + \
+        _f(cf, 'delta alpha_pre sat hue alpha_post') + [('fill', cf * 3)]
+
+
+COLSUM_JOB, WGRAD_JOB, PREP_BWD_JOB, PREP_DESC, SELECT_JOB, SGD_TENSOR, MIX_TARGET, BBOX_STEP, BBOX_CHAIN, PHOTO_IMAGE = (
+    np.dtype(c) for c in (ColsumJob, WgradJob, PrepBwdJob, PrepDesc, SelectJob, SgdTensor, MixTarget, BboxStep, BboxChain,
+                          PhotoImage))
 
 STRUCTS = {   # every struct of the header, by its C name
     'oadg_rpn_level': RpnLevel, 'oadg_rpn_loss_level': RpnLossLevel, 'oadg_roi_assign_image': RoiAssignImage,
     'oadg_roi_target_entry': RoiTargetEntry, 'oadg_roi_sample_image': RoiSampleImage, 'oadg_region_op': RegionOp,
     'oadg_colsum_job': ColsumJob, 'oadg_wgrad_job': WgradJob, 'oadg_prep_bwd_job': PrepBwdJob, 'oadg_prep_desc': PrepDesc,
     'oadg_select_job': SelectJob, 'oadg_sgd_tensor': SgdTensor, 'oadg_mix_target': MixTarget, 'oadg_bbox_step': BboxStep,
-    'oadg_bbox_chain': BboxChain, 'oadg_jpeg_desc': JpegDesc,
+    'oadg_bbox_chain': BboxChain, 'oadg_jpeg_desc': JpegDesc, 'oadg_photo_image': PhotoImage,
 }
 
 # name -> (restype, argtypes); must list every symbol include/oadg_hip.h declares
@@ -296,6 +306,7 @@ SIGNATURES = {
     'oadg_oamix_final_tiles': (ci, [vp, vp, ci, ci, vp, ci, vp, vp, vp, cd, POINTER(cf), POINTER(cf), ci, vp, vp, ci, ci,
                                     ci, vp, ctypes.c_size_t, vp]),
     'oadg_oamix_normalize': (ci, [vp, ci, ci, POINTER(cf), POINTER(cf), ci, vp, ci, ci, ci, vp]),
+    'oadg_photo_normalize_batch': (ci, [vp, ci, vp, POINTER(cf), POINTER(cf), ci, vp, ci, ci, ci, cs, vp]),
 }
 
 

@@ -4,3 +4,4 @@ from .device_pipeline import (Collect, Compose, DefaultFormatBundle, DevicePipel
                               MultiScaleFlipAug, Normalize, Pad, SyntheticCityscapes)
 from .geometric import LoadAnnotations, LoadImageFromFile, RandomFlip, Resize  # noqa: F401
 from .corrupt import Corrupt  # noqa: F401
+from .photometric import CutOut, PhotoMetricDistortion  # noqa: F401

@@ -6,6 +6,8 @@ parse unchanged; they only carry their configuration.  ``DevicePipeline`` reads 
 the collated batch ``train_step`` consumes, with Normalize+Pad fused into the OA-Mix output kernel
 (transforms.py:618-629,699-701; formating.py:217-255,289-357): images leave the pipeline as normalised NHWC
 tensors (logical [N,3,H,W], channels_last), never as host arrays.
+A train pipeline may also name ``PhotoMetricDistortion`` / ``CutOut`` (pipelines/photometric.py) between the geometric steps
+and Normalize: their draws are made per sample and ONE launch of csrc/photo.hip applies them, Normalize and Pad to the batch.
 """
 import ctypes
 import os
@@ -21,6 +23,7 @@ from .corrupt import Corrupt
 from .geometric import RandomFlip, Resize
 from . import oa_mix as _oa_mix
 from .oa_mix import OAMix, _ImageState
+from .photometric import CutOut, PhotoMetricDistortion
 
 
 @PIPELINES.register_module()
@@ -120,7 +123,7 @@ class DevicePipeline:
         self.oamix_workers = max(1, int(oamix_workers if oamix_workers is not None
                                         else os.environ.get('OADG_OAMIX_WORKERS', '1')))
         self._helpers = None
-        ts = Compose(pipeline_cfg).transforms
+        top = ts = Compose(pipeline_cfg).transforms
         # test_robustness.py:269-277 inserts Corrupt right after the image loading step, before MultiScaleFlipAug
         self.corrupt = next((t for t in ts if isinstance(t, Corrupt)), None)
         self.test_aug = next((t for t in ts if isinstance(t, MultiScaleFlipAug)), None)
@@ -135,6 +138,42 @@ class DevicePipeline:
         self.keys = list(collect.keys) if collect else ['img', 'gt_bboxes', 'gt_labels']
         assert self.norm is not None, 'the pipeline needs a Normalize step'
         self.dtype = dtype
+        # the PhotoMetricDistortion / CutOut steps in pipeline order (the order of their draws)
+        self.photo_steps = self._photo_steps(top, ts)
+        self.photo = next((t for t in self.photo_steps if isinstance(t, PhotoMetricDistortion)), None)
+        self.cutout = next((t for t in self.photo_steps if isinstance(t, CutOut)), None)
+        self.cutout_last = len(self.photo_steps) == 2 and self.photo_steps[1] is self.cutout
+
+    def _photo_steps(self, top, ts):
+        """the PhotoMetricDistortion / CutOut steps, in pipeline order, of a train pipeline
+        [Load..., Resize?, RandomFlip?, {PhotoMetricDistortion, CutOut: either order, each at most once}, Normalize, ...];
+        any other arrangement raises a ValueError that names the step, instead of running a pipeline that ignores it"""
+        kinds = (PhotoMetricDistortion, CutOut)
+        if self.test_aug is not None:
+            for t in list(top) + list(ts):
+                if isinstance(t, kinds):
+                    where = 'inside' if t in ts else 'beside'
+                    raise ValueError(f'{type(t).__name__} {where} MultiScaleFlipAug: a train-time augmentation has no place in '
+                                     f'a test pipeline')
+            return []
+        found = {}
+        for i, t in enumerate(ts):
+            if not isinstance(t, kinds):
+                continue
+            name = type(t).__name__
+            if name in found:
+                raise ValueError(f'{name} appears more than once in the pipeline')
+            found[name] = i
+            for j, u in enumerate(ts):
+                if isinstance(u, (Resize, RandomFlip)) and j > i:
+                    raise ValueError(f'{name} in front of {type(u).__name__}: the photometric steps follow the geometric ones '
+                                     f'(they run fused with Normalize, on the resized and flipped image)')
+                if isinstance(u, Normalize) and j < i:
+                    raise ValueError(f'{name} behind Normalize: it works on the 0..255 image, before Normalize')
+                if isinstance(u, OAMix):
+                    raise ValueError(f'{name} together with OAMix: OA-Mix needs the uint8 image and the reference\'s photometric '
+                                     f'step a single img field')
+        return [ts[i] for i in sorted(found.values())]
 
     @torch.no_grad()
     def test_batch(self, imgs_u8, return_fed=False):
@@ -240,10 +279,13 @@ class DevicePipeline:
         gt_labels: list of int64 numpy arrays.  Returns the collated dict for ``train_step``."""
         L = _lib.lib()
         geo_meta = None
-        if self.resize is not None or (self.flip is not None and self.flip.flip_ratio):
+        geometric = self.resize is not None or (self.flip is not None and self.flip.flip_ratio)
+        draws = []       # with a PhotoMetricDistortion / CutOut step: per sample (photo parameters, holes), drawn below
+        if geometric or self.photo_steps:
             # Resize / RandomFlip per sample, in the reference's order (all draws of a sample's geometric steps, then
             # the next sample; OA-Mix draws follow below - a DataLoader worker interleaves them per sample, which is
-            # the same stream split whenever OA-Mix gets its own worker stream)
+            # the same stream split whenever OA-Mix gets its own worker stream); the draws of a sample's PhotoMetricDistortion /
+            # CutOut steps follow its geometric draws, in pipeline order - the holes against the resized extent
             imgs, boxes, geo_meta = [], [], []
             for i in range(imgs_u8.shape[0]):
                 im, bx, meta = imgs_u8[i], np.asarray(gt_bboxes[i], dtype=np.float32), {}
@@ -254,11 +296,18 @@ class DevicePipeline:
                 if self.flip is not None and self.flip.flip_ratio:
                     im, bx, m = self.flip(im, bx)
                     meta.update(m)
+                if self.photo_steps:
+                    drawn = {t: t.draw() if t is self.photo else t.draw(int(im.shape[0]), int(im.shape[1]))
+                             for t in self.photo_steps}
+                    draws.append((drawn.get(self.photo), drawn.get(self.cutout)))
                 imgs.append(im)
                 boxes.append(bx)
                 geo_meta.append(meta)
-            imgs_u8 = torch.stack(imgs) if all(im.shape == imgs[0].shape for im in imgs) else imgs
-            gt_bboxes = boxes
+            if geometric:
+                imgs_u8 = torch.stack(imgs) if all(im.shape == imgs[0].shape for im in imgs) else imgs
+                gt_bboxes = boxes
+            else:
+                geo_meta = None
         # per-sample image shapes (the reference's multi-scale Resize draws a scale per SAMPLE, transforms.py:177-243):
         # every image is padded to its own multiple of size_divisor (Pad, transforms.py:699-701) and the batch tensor
         # takes the largest padded extent, zero-filled right / bottom - what mmcv's collate does with padded
@@ -287,11 +336,20 @@ class DevicePipeline:
             img._oadg_batch = both
         else:
             img = mk()
-        for i in range(N):   # physical NHWC slice i is contiguous
-            check(L.oadg_oamix_normalize(ptr(imgs_u8[i].contiguous() if per_image else imgs_u8[i]), shapes[i][0],
-                                         shapes[i][1], mean, stdinv, int(na['to_rgb']),
-                                         ctypes.c_void_p(img.data_ptr() + i * img.stride(0) * img.element_size()),
-                                         dt, Hp, Wp, stream_ptr()), 'oadg_oamix_normalize')
+        if self.photo_steps:
+            # CutOut, PhotoMetricDistortion, Normalize and Pad of the whole batch in one launch (csrc/photo.hip)
+            import oadg_photo
+            fill = self.cutout.fill(on_uint8=not self.cutout_last) if self.cutout is not None else (0, 0, 0)
+            oadg_photo.photo_normalize_batch(
+                [imgs_u8[i].contiguous() for i in range(N)],
+                [oadg_photo.sample(p, r, fill, self.cutout_last) for p, r in draws],
+                na['mean'], na['stdinv'], na['to_rgb'], img.permute(0, 2, 3, 1))
+        else:
+            for i in range(N):   # physical NHWC slice i is contiguous
+                check(L.oadg_oamix_normalize(ptr(imgs_u8[i].contiguous() if per_image else imgs_u8[i]), shapes[i][0],
+                                             shapes[i][1], mean, stdinv, int(na['to_rgb']),
+                                             ctypes.c_void_p(img.data_ptr() + i * img.stride(0) * img.element_size()),
+                                             dt, Hp, Wp, stream_ptr()), 'oadg_oamix_normalize')
         out['img'] = img
         # the host copies of the gt boxes travel in img_metas: the random-proposal generator and OA-Mix need
         # them on the host, and reading them back from the device would stall the stream
