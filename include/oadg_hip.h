@@ -641,6 +641,50 @@ int oadg_jpeg_pixels_bgr(const int16_t* coef, const oadg_jpeg_desc* desc, int n,
 int oadg_jpeg_decode_bgr(const char* path, uint8_t* out, int H, int W);
 
 /* ------------------------------------------------------------------------------------------------
+ * jpeg_compression and pixelate of the robustness benchmark on the DEVICE (csrc/recompress.hip), byte for byte as Pillow
+ *   every entry below: `Corrupt`  mmdet/datasets/pipelines/transforms.py:1277-1317 -> imagecorruptions.corrupt
+ *             (jpeg_compression: Image.save('JPEG', quality) + Image.open; pixelate: resize(BOX) + resize(NEAREST))
+ * Called from oadg_recompress.py only (the device route of Corrupt.batch for the names of DEVICE_CODEC_CORRUPTIONS).
+ *
+ * JPEG round trip without the entropy coder: colour conversion, 4:2:0 downsampling with libjpeg's edge padding, islow
+ * forward DCT, quantize | dequantize, then the inverse half the file reader above decodes with.  in / out: uint8
+ * [n][H][W][3], channel 0 is what the colour conversion takes for R, on both sides.  qt: two tables of 64 uint16 in
+ * natural (row-major) order, luminance then chrominance, every entry >= 1 - libjpeg's tables for the quality, built by the
+ * caller.  flags: int32 [n]; flags[i] = 1 when a block of image i lies outside the bounds inside which libjpeg-turbo's C
+ * and SIMD IDCT forms agree (every dequantized coefficient and every column-pass value within +-16383, every descaled
+ * sample within [-512, 511]): the caller recomputes that image with Pillow.
+ *   oadg_jpeg_recompress_workspace_bytes  bytes of component planes n images of H x W need (0: arguments the call refuses)
+ *   oadg_jpeg_recompress_u8      DEVICE: two launches for the batch and a memset of flags; planes: the workspace (8-byte
+ *                                aligned; OADG_ESIZE when planes_bytes is short).  Allocates nothing, does not synchronise.
+ *   oadg_jpeg_recompress_host    HOST twin (the same source): numpy buffers in, no GPU
+ *   oadg_jpeg_recompress_bounds_host   the bounds above on one block of 64 dequantized coefficients, column-major (element
+ *                                u * 8 + v = horizontal frequency u, vertical v): 0 inside all three, else bit 0 a
+ *                                coefficient, bit 1 a column-pass value, bit 2 a sample is outside */
+size_t oadg_jpeg_recompress_workspace_bytes(int n, int H, int W);
+int oadg_jpeg_recompress_u8(const uint8_t* in, int n, int H, int W, const uint16_t* qt, uint8_t* planes,
+                            size_t planes_bytes, uint8_t* out, int32_t* flags, void* stream);
+int oadg_jpeg_recompress_host(const uint8_t* in, int n, int H, int W, const uint16_t* qt_host, uint8_t* out,
+                              int32_t* flags);
+int oadg_jpeg_recompress_bounds_host(const int32_t* dequantized);
+/* Pillow's resampling of uint8 [n][H][W][3] images with tables the caller computes in double as Pillow does
+ * (precompute_coeffs + normalize_coeffs_8bpc; the accumulating scan of ImagingScaleAffine):
+ *   oadg_pil_box_resize_u8   ImagingResampleHorizontal_8bpc (axis 1: dst [n][H][out_size][3]) or Vertical_8bpc (axis 0: dst
+ *                            [n][out_size][W][3]): output index i sums the pixels bounds[2 i] ... + bounds[2 i + 1] - 1 of
+ *                            its line with the weights coeffs[i * ksize ...] (22 fractional bits),
+ *                            clip8(((1 << 21) + sum) >> 22), the sum in 64 bits
+ *   oadg_pil_nearest_u8      resize(NEAREST): dst [n][H][W][3], pixel (y, x) = src [n][h][w][3] at (ymap[y], xmap[x]), 0
+ *                            where an index lies outside the source
+ *   oadg_pil_pixelate_host   HOST twin of the chain (the same source): horizontal pass to ow columns, vertical pass to oh
+ *                            rows, NEAREST back to H x W */
+int oadg_pil_box_resize_u8(const uint8_t* src, uint8_t* dst, int n, int H, int W, int axis, int out_size,
+                           const int32_t* bounds, const int32_t* coeffs, int ksize, void* stream);
+int oadg_pil_nearest_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w, int H, int W, const int32_t* ymap,
+                        const int32_t* xmap, void* stream);
+int oadg_pil_pixelate_host(const uint8_t* in, int n, int H, int W, int oh, int ow, const int32_t* xbounds,
+                           const int32_t* xcoeffs, int xksize, const int32_t* ybounds, const int32_t* ycoeffs, int yksize,
+                           const int32_t* ymap, const int32_t* xmap, uint8_t* out);
+
+/* ------------------------------------------------------------------------------------------------
  * Robustness-benchmark corruptions (HOST functions, no device work; csrc/corrupt_host.hip) - the two sequential
  * per-pixel loops of `Corrupt`, mmdet/datasets/pipelines/transforms.py:1277-1317 -> imagecorruptions.corrupt
  * (third party, v1.1.2), tools/analysis_tools/test_robustness.py:222-235

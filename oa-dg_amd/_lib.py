@@ -287,6 +287,13 @@ SIGNATURES = {
     'oadg_jpeg_entropy_decode': (ci, [c_char_p, ci, ci, vp, cs, vp]),
     'oadg_jpeg_pixels_bgr': (ci, [vp, vp, ci, ctypes.c_longlong, vp, vp, ci, ci, vp]),
     'oadg_jpeg_decode_bgr': (ci, [c_char_p, vp, ci, ci]),
+    'oadg_jpeg_recompress_workspace_bytes': (cs, [ci, ci, ci]),
+    'oadg_jpeg_recompress_u8': (ci, [vp, ci, ci, ci, vp, vp, cs, vp, vp, vp]),
+    'oadg_jpeg_recompress_host': (ci, [vp, ci, ci, ci, vp, vp, vp]),
+    'oadg_jpeg_recompress_bounds_host': (ci, [vp]),
+    'oadg_pil_box_resize_u8': (ci, [vp, vp, ci, ci, ci, ci, ci, vp, vp, ci, vp]),
+    'oadg_pil_nearest_u8': (ci, [vp, vp, ci, ci, ci, ci, ci, vp, vp, vp]),
+    'oadg_pil_pixelate_host': (ci, [vp, ci, ci, ci, ci, ci, vp, vp, ci, vp, vp, ci, vp, vp, vp]),
     'oadg_glass_shuffle_u8': (ci, [vp, ci, ci, ci, ci, ci, vp]),
     'oadg_chamfer_l2_5x5': (ci, [vp, ci, ci, vp]),
     'oadg_corrupt_correlate1d': (ci, [vp, ci, vp, vp, ci, ci, ci, ci, ci, vp, ci, ci, vp]),

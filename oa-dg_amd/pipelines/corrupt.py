@@ -24,8 +24,12 @@ statistics of the noise models.  Random draws come from numpy's global stream, a
 offsets, which the package draws from numba's private generator inside its compiled loop (no stream to replay).
 Evaluation-time code (the reference corrupts numpy images inside its DataLoader workers too); it is not part of the
 training hot path.  ``Corrupt.batch`` of a batch resident on the GPU runs the names of ``DEVICE_CORRUPTIONS`` on the device
-(pipelines/corrupt_device.py, csrc/corrupt.hip: the same bytes and the same draws from numpy's stream); the other names,
-CPU batches, ``Corrupt.__call__`` and every batch when ``OADG_DEVICE_CORRUPT=0`` run on the host.
+(pipelines/corrupt_device.py, csrc/corrupt.hip: the same bytes and the same draws from numpy's stream) and the two names of
+``DEVICE_CODEC_CORRUPTIONS``, whose host path is nothing but a Pillow call, through csrc/recompress.hip (oadg_recompress.py:
+a JPEG round trip without the entropy coder and Pillow's fixed-point BOX / NEAREST resampling, the same bytes; Pillow stays
+the authority: an image the device flags - a block where libjpeg-turbo's IDCT forms could disagree - and a batch it declines
+are corrupted below).  The other names, CPU batches, ``Corrupt.__call__`` and every batch when ``OADG_DEVICE_CORRUPT=0`` run on
+the host.
 """
 import math
 import os
@@ -40,12 +44,15 @@ IMPLEMENTED = ('gaussian_noise', 'shot_noise', 'impulse_noise', 'defocus_blur', 
                'speckle_noise', 'gaussian_blur', 'spatter', 'saturate')
 NEEDS_ASSETS = ('frost',)          # runs when OADG_FROST_DIR holds the package's six frost photographs
 # Corrupt.batch on a GPU batch: these run on the device (byte-identical), the others stay on the host - shot_noise (its
-# Poisson draws depend on the pixels), pixelate and jpeg_compression (Pillow), spatter (connected components), frost
-# (photographs), the noise models, contrast and fog
+# Poisson draws depend on the pixels), pixelate and jpeg_compression (Pillow: see DEVICE_CODEC_CORRUPTIONS), spatter
+# (connected components), frost (photographs), the noise models, contrast and fog
 DEVICE_CORRUPTIONS = ('gaussian_blur', 'glass_blur', 'defocus_blur', 'motion_blur', 'zoom_blur', 'snow', 'brightness',
                       'saturate', 'elastic_transform')
 HOST_CORRUPTIONS = ('gaussian_noise', 'shot_noise', 'impulse_noise', 'speckle_noise', 'contrast', 'fog', 'pixelate',
                     'jpeg_compression', 'spatter', 'frost')
+# host names with a device route all the same (oadg_recompress.py, csrc/recompress.hip): pure integer arithmetic, no draw;
+# Pillow is the fall-back for an image the device flags and for a batch it declines
+DEVICE_CODEC_CORRUPTIONS = ('pixelate', 'jpeg_compression')
 
 
 def _rgb2hsv(x):
@@ -539,16 +546,28 @@ class Corrupt:
 
     def batch(self, imgs_u8):
         """a resident uint8 batch.  On the GPU, a name of DEVICE_CORRUPTIONS is corrupted there (pipelines/corrupt_device.py,
-        byte for byte and draw for draw as below) unless OADG_DEVICE_CORRUPT=0; otherwise it is corrupted on the host image
-        by image (as the reference's workers do) and uploaded again"""
+        byte for byte and draw for draw as below) and so is a name of DEVICE_CODEC_CORRUPTIONS (oadg_recompress.py; the images
+        it flags are corrupted below and written into its result, a batch it declines takes the host path) unless
+        OADG_DEVICE_CORRUPT=0; otherwise it is corrupted on the host image by image (as the reference's workers do) and
+        uploaded again"""
         import torch
         n = int(imgs_u8.shape[0])
-        if imgs_u8.is_cuda and self.corruption in DEVICE_CORRUPTIONS and self.severity != 0 and \
-                os.environ.get('OADG_DEVICE_CORRUPT', '1') != '0':
+        on_device = imgs_u8.is_cuda and self.severity != 0 and os.environ.get('OADG_DEVICE_CORRUPT', '1') != '0'
+        if on_device and self.corruption in DEVICE_CORRUPTIONS:
             from .corrupt_device import corrupt_batch
             out = corrupt_batch(imgs_u8, self.corruption, self.severity)
             Corrupt.runs['device'] += n
             return out
+        if on_device and self.corruption in DEVICE_CODEC_CORRUPTIONS:
+            import oadg_recompress
+            done = oadg_recompress.corrupt_batch(imgs_u8, self.corruption, self.severity)
+            if done is not None:
+                out, flagged = done
+                for i in flagged:
+                    out[i] = torch.tensor(corrupt(imgs_u8[i].cpu().numpy(), self.corruption, self.severity), device=out.device)
+                Corrupt.runs['device'] += n - len(flagged)
+                Corrupt.runs['host'] += len(flagged)
+                return out
         host = imgs_u8.cpu().numpy()
         out = np.stack([corrupt(im, self.corruption, self.severity) for im in host])
         Corrupt.runs['host'] += n

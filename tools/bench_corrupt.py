@@ -1,15 +1,18 @@
 """The robustness benchmark's on-the-fly corruptions (test_robustness.py --load-dataset original): the host path
-(``corrupt()``: numpy / scipy, one image at a time on one thread) against the device path of ``Corrupt.batch``
-(pipelines/corrupt_device.py, csrc/corrupt.hip).  Prints one JSON line.
+(``corrupt()``: numpy / scipy / Pillow, one image at a time on one thread) against the device path of ``Corrupt.batch``
+(pipelines/corrupt_device.py, csrc/corrupt.hip; for pixelate and jpeg_compression oadg_recompress.py, csrc/recompress.hip).
+Prints one JSON line.
 
 usage: python tools/bench_corrupt.py [--batch 4] [--reps 3] [--severities 3 5] [--names ...]
 
 Per benchmark name and severity, on synthetic 1024x2048 images (lowpass noise):
   host_s_per_image: corrupt() on one image, one thread
-  device: for the names of DEVICE_CORRUPTIONS, a resident batch of --batch images through Corrupt.batch after one
-      warm-up, between synchronisations, median of --reps: ms_per_image (wall), split into host_ms_per_image (draws,
-      tables, glass_blur's shuffle: corrupt_device.STATS) and device_ms_per_image (the rest: launches, uploads,
-      kernels); byte_equal: image 0 of the batch equals the host result under the same seed
+  device: for the names of DEVICE_CORRUPTIONS and DEVICE_CODEC_CORRUPTIONS, a resident batch of --batch images through
+      Corrupt.batch after one warm-up, between synchronisations, median of --reps: ms_per_image (wall), split into
+      host_ms_per_image (draws, tables, glass_blur's shuffle: corrupt_device.STATS; the codec names' small tables are not
+      timed apart and count as device time) and device_ms_per_image (the rest: launches, uploads, kernels, the read of the
+      codec route's flags); byte_equal: image 0 of the batch equals the host result under the same seed; host_fallbacks
+      (codec names): images of the timed batches the device handed back to Pillow
   projected_hours: the full benchmark (15 names x 5 severities x 500 images), each name at the mean of its measured
       severities, host only and with the device routing; frost (photographs not in the repository) is left out of both
 """
@@ -49,7 +52,7 @@ def main():
     a = p.parse_args()
     import torch
     from oadg_amd.pipelines import corrupt_device
-    from oadg_amd.pipelines.corrupt import DEVICE_CORRUPTIONS, NEEDS_ASSETS, Corrupt, corrupt
+    from oadg_amd.pipelines.corrupt import DEVICE_CODEC_CORRUPTIONS, DEVICE_CORRUPTIONS, NEEDS_ASSETS, Corrupt, corrupt
     imgs = images(a.batch)
     gpu = torch.cuda.is_available()
     x = torch.from_numpy(imgs).cuda() if gpu else None
@@ -64,12 +67,12 @@ def main():
             t = time.perf_counter()
             ref = corrupt(imgs[0], name, s)
             r = dict(host_s_per_image=round(time.perf_counter() - t, 4))
-            if gpu and name in DEVICE_CORRUPTIONS:
+            if gpu and (name in DEVICE_CORRUPTIONS or name in DEVICE_CODEC_CORRUPTIONS):
                 c = Corrupt(name, s)
                 np.random.seed(0)
                 out = c.batch(x)
                 r['byte_equal'] = bool(np.array_equal(out[0].cpu().numpy(), ref))
-                walls, hosts = [], []
+                walls, hosts, fell_back = [], [], Corrupt.runs['host']
                 for _ in range(a.reps):
                     torch.cuda.synchronize()
                     h0 = corrupt_device.STATS['host_s']
@@ -82,6 +85,8 @@ def main():
                 wall, host = walls[k] / a.batch * 1e3, hosts[k] / a.batch * 1e3
                 r['device'] = dict(ms_per_image=round(wall, 3), host_ms_per_image=round(host, 3),
                                    device_ms_per_image=round(wall - host, 3))
+                if name in DEVICE_CODEC_CORRUPTIONS:
+                    r['device']['host_fallbacks'] = Corrupt.runs['host'] - fell_back
             per[s] = r
         res['names'][name] = per
 
